@@ -6,7 +6,11 @@ One "step" = one pass of the hot path over one batch: `tafl_mcts_run` of S simul
 per GPU, from the start position (BASELINE.json configs[2]; configs[3] is this workload at N=8, 524 288 games).
 States are resident in HBM before the timed region; nothing crosses PCIe inside it.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--dump-outputs DIR` then writes what the last
+timed step computed (dump_outputs) as DIR/<name>.npy.  `--full` adds everything else the line can carry, measured after the
+headline timed region: `variants` and `cpu_baseline` below.
 
 N > 1 runs one process per GPU, each with its own shard of global game ids and NO collective on the data path (a barrier
 and a max-reduce of the elapsed time only).  Two ways to get there:
@@ -18,9 +22,9 @@ and a max-reduce of the elapsed time only).  Two ways to get there:
 
 Prints ONE JSON line on rank 0 (contract in the task statement) with extra objects:
   roofline      dominant kernel: algorithmic HBM bytes per step / live HIP-event time of its launches
-  cpu_baseline  the oracle (literal C restatement of the reference rules crate + mcts.py arithmetic) timed on the
+  cpu_baseline  (--full) the oracle (literal C restatement of the reference rules crate + mcts.py arithmetic) timed on the
                 host, 1 thread, on a bounded sample of the same workload (+ `all_cores`, + BASELINE configs[0])
-  variants      the rest of SURVEY.md section 8d, measured after the headline timed region (N=1 only): S=256 / S=1000,
+  variants      (--full) the rest of SURVEY.md section 8d, measured after the headline timed region (N=1 only): S=256 / S=1000,
                 13x13 (configs[4]), and the streamed configs[1] kernels at 4 096 and 65 536 games, each with its roofline
 """
 import argparse
@@ -236,6 +240,39 @@ def mcts_roofline(stats, kt, steps, side, traffic=None, traffic_source=None):
     return r, kname, bps, d_bar, c_bar
 
 
+def dump_outputs(batch, out_dir, max_children, sample_games=8192, budget_bytes=48 << 20):
+    """What a caller of the timed path reads back after its last step (tafl_mcts_root_children), as DIR/<name>.npy: for every game
+    the number of visited root children and the first most visited one in canonical order; for a fixed sample of games (seed 0) all
+    their visited root children in canonical order (action, visits, Q; padded with -1 / 0 / 0).  Counts and action indices are exact
+    in float32; Q keeps its float64 bits."""
+    import numpy as np
+
+    from alphazeroforhnefatafl_amd.abi import TaflRootChild as T
+    kids, cnt = batch.mcts_root_children(max_children)
+    rec = np.frombuffer(kids, dtype=np.dtype({"names": ["action", "visits", "q"], "formats": ["<u4", "<u4", "<f8"],
+                                              "offsets": [T.action.offset, T.visits.offset, T.q.offset],
+                                              "itemsize": C.sizeof(T)})).reshape(batch.n, max_children)
+    n = np.frombuffer(cnt, dtype=np.uint32)
+    used = np.arange(max_children)[None, :] < n[:, None]
+    action = np.where(used, rec["action"].astype(np.int64), -1)
+    visits = np.where(used, rec["visits"], 0)
+    q = np.where(used, rec["q"], 0.0)
+    rows = np.arange(batch.n)
+    best = visits.argmax(axis=1)
+    k = min(batch.n, sample_games, budget_bytes // (16 * max_children))   # 4 + 4 + 8 bytes per child slot
+    sample = np.sort(np.random.default_rng(0).choice(batch.n, size=k, replace=False))
+    arrays = {"root_children_count": n.astype(np.float32),
+              "root_best_action": action[rows, best].astype(np.float32),
+              "root_best_visits": visits[rows, best].astype(np.float32),
+              "sample_games": sample.astype(np.float64),
+              "sample_root_action": action[sample].astype(np.float32),
+              "sample_root_visits": visits[sample].astype(np.float32),
+              "sample_root_q": q[sample].astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def streamed_variant(logic, fen, side, G):
     """BASELINE configs[1] workload (games advanced by (i mod 64) seeded random plies): kernel-only HIP-event times of the
     streamed entry points with their algorithmic HBM rates (372 B / 136 B / 68 B per game on 11x11)."""
@@ -439,8 +476,12 @@ def main():
     ap.add_argument("--max-plies", type=int, default=512)
     ap.add_argument("--cpuct", type=float, default=1.0)
     ap.add_argument("--seed", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the `variants` object (S=256/1000, 13x13, streamed kernels)")
+    ap.add_argument("--full", action="store_true", help="after the headline line's own measurement, also measure the `variants` and "
+                    "`cpu_baseline` objects (N=1 only); a plain run does neither")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (rank 0's games) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the `cpu_baseline` object")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the `variants` object (S=256/1000, 13x13, streamed kernels)")
     ap.add_argument("--board", default="copenhagen11", choices=list(BOARDS),
                     help="copenhagen11 = the headline workload (BASELINE configs[2]); copenhagen13 = configs[4] (U256 multi-word path)")
     ap.add_argument("--pipeline", type=int, default=0, help="tuning: MCTS pipeline (0 default, 1 fused kernel, 2 two-kernel); results do not depend on it")
@@ -571,10 +612,12 @@ def main():
                 ach = insts / (elapsed / args.steps)
                 out["roofline_valu"] = {"bound": "valu_issue", "achieved": ach, "peak": VALU_ISSUE_PEAK, "unit": "wave64 VALU instructions/s", "frac": ach / VALU_ISSUE_PEAK,
                                         "instructions_per_step": insts, "source": "profiles/valu_k_mcts_rollout.json: " + pj.get("source", "")}
+        if args.dump_outputs:
+            dump_outputs(batch, args.dump_outputs, min(args.sims, 512))
         batch.close()
-        if world == 1 and not args.no_variants and headline:
+        if args.full and world == 1 and not args.no_variants and headline:
             out["variants"] = run_variants(args, torch)
-        if world == 1 and not args.no_cpu_baseline and args.board == "copenhagen11":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.board == "copenhagen11":
             out["cpu_baseline"] = cpu_baseline(args.sims, args.cpuct, args.seed, args.max_plies)
         out["digest"] = make_digest(out)                     # last key on purpose
         print(json.dumps(out), flush=True)

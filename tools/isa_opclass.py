@@ -31,7 +31,7 @@ def classify(op, operands=""):
             return "OTHER"
         if op.startswith(("s_branch", "s_cbranch")):
             return "BRANCH"
-        if op.startswith(("s_load", "s_buffer_load", "s_store", "s_memtime", "s_memrealtime", "s_dcache")):
+        if op.startswith(("s_load", "s_buffer_load", "s_memtime", "s_memrealtime", "s_dcache")):   # the project's kernels only read through SMEM
             return "MEM"
         return "SALU"
     if op.startswith(("global_", "flat_", "buffer_", "scratch_", "ds_")):

@@ -7,9 +7,9 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/r02
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 $R/bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 echo "bench done"
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 1 --warmup 1 --no-cpu-baseline > $O/kt.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -- python3 $R/bench.py --steps 1 --warmup 1 --full --no-cpu-baseline > $O/kt.log 2>&1
 echo "kt done"
 # the same kernel trace for the headline workload alone (no variants): its per-kernel averages are the ones to compare with the HIP-event
 # averages in that run's own bench line

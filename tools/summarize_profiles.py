@@ -2,8 +2,8 @@
 """Turn the rocprofv3 outputs of one profiling session into the summaries kept under profiles/.
 
 Inputs (directories written on the GPU box, newest file of each kind is used):
-  --kt     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline
-  --fetch  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline
+  --kt     rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline
+  --fetch  rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d DIR -- python3 bench.py --steps 1 --warmup 0 --full --no-cpu-baseline
   --write  rocprofv3 --pmc WRITE_SIZE ... (same command)
   --sq     rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_SMEM SQ_INSTS_VMEM GRBM_GUI_ACTIVE ...
 Counter passes are separate runs (never combined with API traces), summed over all dispatches of a kernel in ONE bench step.
