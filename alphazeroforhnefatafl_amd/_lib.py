@@ -66,6 +66,11 @@ SYMBOLS = [
     ("tafl_gmcts_policy", _i32, [_vp, _dbl, _vp, _i32]),
     ("tafl_gmcts_policy_ex", _i32, [_vp, _dbl, _u64, _u64, _vp, _i32]),
     ("tafl_gmcts_get_stats", _i32, [_vp, _P(TaflGmctsStats)]),
+    ("tafl_mcts_advance", _i32, [_vp, _P(_u32), _P(TaflPlay), _P(TaflEffects)]),
+    ("tafl_mcts_tree_nodes", _i32, [_vp, _P(_u32)]),
+    ("tafl_gmcts_begin_ex", _i32, [_vp, _u32, _u32, _u32]),
+    ("tafl_gmcts_advance", _i32, [_vp, _P(_u32), _P(TaflPlay), _P(TaflEffects)]),
+    ("tafl_gmcts_tree_nodes", _i32, [_vp, _P(_u32)]),
     ("tafl_replay_append", _i32, [C.c_char_p, _P(_u8), _u8, _P(_u8), _u32, _u8, _u8, _u64]),
     ("tafl_replay_append_batch", _i32, [C.c_char_p, _P(_u8), _u8, _u32, _P(_u8), _P(_u32), _P(_u8), _P(_u8), _u64]),
     ("tafl_replay_read", _i32, [C.c_char_p, _u8, _u32, _P(_u8), _P(_u8), _u32, _P(_u32), _P(_u8), _P(_u8), _P(_u32)]),

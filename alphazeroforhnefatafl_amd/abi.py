@@ -55,6 +55,10 @@ MAX_LIMBS = 4
 
 # tafl_mcts_params.flags (include/taflhip.h): tuning fields choose how a search is executed, never what it returns
 MCTS_FLAG_FPU_INF = 0x1          # src/mcts.rs:49-51,187: unvisited actions score +inf, new nodes start with visits 1 (oracle-pinned only)
+MCTS_FLAG_KEEP_TREE = 0x2        # continue the retained tree (subtree reuse, include/taflhip.h TAFL_MCTS_FLAG_KEEP_TREE)
+MCTS_FLAGS_KNOWN = 0x000FFFF3
+GMCTS_KEEP_TREE = 0x1
+ACTION_NONE = 0xFFFFFFFF         # tafl_mcts_advance / tafl_gmcts_advance: leave this game alone
 MCTS_PIPELINE_DEFAULT, MCTS_PIPELINE_FUSED, MCTS_PIPELINE_TWO_KERNEL = 0, 1, 2
 
 

@@ -537,6 +537,89 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_play_best(Consts<NL> C, Mct
     if (out_plays) out_plays[g] = p;
 }
 
+// ---- subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE) ------------------------------------------------------------------
+// keep-init: a search that continues the retained tree (k_mcts_init for the games without one)
+template <int NLS, int WS, int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_keep_init(Consts<NL> C, const Quad* soa, MctsMem M) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    if (M.node_top[g] == 0) { DState<NL> st; load_batch_state<NLS, WS, NL, W>(soa, M.G, g, C.n, st); Ops<NL, W>::mcts_init_game(M, g, st, C); }
+    else Ops<NL, W>::mcts_keep_init(M, g);
+}
+// out[0] = max a[g], out[1] = max b[g] (kept nodes and edges of a retained tree: what the next search's arena must hold beside its own)
+__global__ __launch_bounds__(256) void k_max2(const uint32_t* a, const uint32_t* b, uint32_t n, uint32_t* out) {
+    const uint32_t g = blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    atomicMax(&out[0], a[g]); atomicMax(&out[1], b[g]);
+}
+// the play of tafl_mcts_advance / tafl_gmcts_advance on the batch state (layout <NL, W>): do_play (logic.rs:827-834) of a dense action
+// index, exactly tafl_step; returns true when the play was made
+template <int NL, int W>
+__device__ __forceinline__ bool advance_play(const Consts<NL>& C, DState<NL>& st, uint32_t a, uint32_t A, tafl_play& p, tafl_effects& e) {
+    using O = Ops<NL, W>;
+    O::caps_to_effects(bz<NL>(), 0, e);
+    p.from_row = p.from_col = p.axis = 0; p.disp = 0;
+    if (a == TAFL_ACTION_NONE || TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { O::status_to_effects(st, TAFL_PLAY_GAME_OVER, e); return false; }
+    if (a >= A) { O::status_to_effects(st, TAFL_PLAY_OUT_OF_BOUNDS, e); return false; }
+    const tafl_play pl = O::to_play(O::move_of_action(a, C));
+    DState<NL> s2 = st;
+    O::step(s2, pl, C, &e);
+    if (e.code != TAFL_PLAY_OK) return false;
+    st = s2; p = pl;
+    return true;
+}
+template <int NL>
+__device__ __forceinline__ bool same_state(const Quad* rec, const DState<NL>& st) {
+    uint32_t v[StateIO<NL>::WORDS]; StateIO<NL>::pack(st, v);
+    bool same = true;
+    TAFL_UNROLL for (int q = 0; q < StateIO<NL>::QUADS; ++q) {
+        const Quad t = rec[q];
+        same = same && t.x == v[4 * q] && t.y == v[4 * q + 1] && t.z == v[4 * q + 2] && t.w == v[4 * q + 3];
+    }
+    return same;
+}
+// tafl_mcts_advance, one game per lane: play actions[g] (NULL: the most visited root child, first maximum) on the batch state and re-root
+// the retained tree at that child (Ops::mcts_reroot).  live == 0: the arena holds no tree for these states (every game gets a fresh root).
+// Every game's edges end up in `dst` (the caller swaps the arenas).  bad[0] counts kept roots whose state differs from the new batch state
+// (never expected: such a game gets a fresh root).  Batch layout <NLS, WS>, arena layout <NL, W>.
+template <int NLS, int WS, int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_advance(Consts<NLS> Cb, Consts<NL> Ca, MctsMem M, Quad* soa, Edge* dst, uint32_t* idmap,
+                                                             const uint32_t* actions, int live, uint32_t A, tafl_play* out_plays, tafl_effects* eff, uint32_t* bad) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    using OA = Ops<NL, W>;
+    const NodeHdr h = M.hdr[g];
+    const Edge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+    uint32_t a = actions ? actions[g] : TAFL_ACTION_NONE, child = 0;
+    if (live) {
+        uint32_t best = 0;
+        for (uint32_t j = 0; j < h.m; ++j) {
+            const Edge e = eb[j];
+            const NodeHdr ch = M.hdr[(size_t)e.child * M.G + g];
+            Move m; m.from = ch.mv_from; m.dir = ch.mv_dir; m.dist = ch.mv_dist; m.to = 0;
+            const uint32_t ea = OA::action_of(m, Ca);
+            if (actions ? (ea == a && child == 0) : e.n > best) { best = e.n; child = e.child; a = ea; }
+        }
+    }
+    DState<NLS> st; StateIO<NLS>::load_soa(soa, M.G, g, st);
+    tafl_play p; tafl_effects e;
+    const bool played = advance_play<NLS, WS>(Cb, st, a, A, p, e);
+    if (played) StateIO<NLS>::store_soa(soa, M.G, g, st);
+    const bool alone = !played && (a == TAFL_ACTION_NONE || e.code == TAFL_PLAY_GAME_OVER);      // nothing to play: the game is left alone
+    if (live && alone) OA::mcts_keep_edges(M, dst, g);
+    else {
+        DState<NL> ast; load_batch_state<NLS, WS, NL, W>(soa, M.G, g, Cb.n, ast);
+        bool fresh = !(live && played && child != 0);
+        if (!fresh) {
+            OA::mcts_reroot(M, dst, idmap, g, child);
+            if (!same_state<NL>(M.node_state + (size_t)g * StateIO<NL>::QUADS, ast)) { atomicAdd(bad, 1u); fresh = true; }
+        }
+        if (fresh) OA::mcts_init_game(M, g, ast, Ca);           // never visited, an illegal action, or no tree: a root the tables have never seen
+    }
+    if (out_plays) out_plays[g] = p;
+    if (eff) eff[g] = e;
+}
+
 template <int NL, int W>
 __global__ __launch_bounds__(256) void k_encode_boards(Consts<NL> C, const Quad* soa, uint32_t n_games, uint8_t* out) {
     const uint32_t nn = C.n * C.n;
@@ -684,6 +767,10 @@ struct tafl_batch {
     // guided MCTS (external evaluator)
     GuidedMem gmem; bool g_has; uint32_t g_max_sims;
     DevBuf g_node_state, g_hdr, g_pedge, g_edges, g_node_top, g_edge_top, g_leaf, g_kind, g_fault, g_sims, g_stats, g_priors, g_values, g_boards, g_sides, g_wait;
+    // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
+    // arena and the id map of a re-root; a small read-back buffer
+    bool tree_live, g_tree_live;
+    DevBuf edges_alt, idmap, g_edges_alt, g_idmap, small;
 };
 
 static int quads_of(const tafl_ctx* c) { return (2 * (int)c->nl + 8) / 4; }
@@ -862,6 +949,7 @@ int tafl_batch_create(tafl_ctx* c, uint32_t n, tafl_batch** out) {
     tafl_batch* b = new (std::nothrow) tafl_batch();
     if (!b) return fail(TAFL_ERR_OOM, "out of host memory");
     b->ctx = c; b->n = n; b->has_mem = false; b->reserved_sims = 0; b->ran = false; b->soa = nullptr; b->g_has = false; b->g_max_sims = 0; b->trace_rounds = 0;
+    b->tree_live = false; b->g_tree_live = false;
 #ifdef TAFL_EXPERIMENT_SPEC_K
     b->spec_k = TAFL_EXPERIMENT_SPEC_K;      // measurement builds only
 #else
@@ -892,7 +980,8 @@ int tafl_batch_destroy(tafl_batch* b) {
                       &b->children, &b->children_n, &b->visits, &b->sim_next, &b->spec_state, &b->spec_meta, &b->spec_value, &b->spec_kind, &b->spec_reason,
                       &b->spec_plies, &b->spec_ref, &b->spec_cls, &b->spec_pend, &b->spec_bias, &b->best_plays, &b->best_visits, &b->enc, &b->policy, &b->work, &b->work_count, &b->trace, &b->ctrl, &b->sim_base, &b->sp_moves_done, &b->sp_start_round, &b->sp_plays,
                       &b->g_node_state, &b->g_hdr, &b->g_pedge, &b->g_edges, &b->g_node_top, &b->g_edge_top, &b->g_leaf, &b->g_kind, &b->g_fault, &b->g_sims,
-                      &b->g_stats, &b->g_priors, &b->g_values, &b->g_boards, &b->g_sides, &b->g_wait};
+                      &b->g_stats, &b->g_priors, &b->g_values, &b->g_boards, &b->g_sides, &b->g_wait,
+                      &b->edges_alt, &b->idmap, &b->g_edges_alt, &b->g_idmap, &b->small};
     for (DevBuf* d : bufs) d->release();
     delete b;
     return TAFL_OK;
@@ -907,12 +996,22 @@ int tafl_sync(tafl_ctx* c) {
     return TAFL_OK;
 }
 
+int tafl_mcts_wait(tafl_batch* b);
+// every write to the batch states joins a search in flight first (the search reads them, and its tree must not be dropped under it) and
+// drops the retained trees (TAFL_MCTS_FLAG_KEEP_TREE): they belong to the states before the write
+static int batch_write(tafl_batch* b) {
+    if (b->plan.active) { const int rc = tafl_mcts_wait(b); if (rc) return rc; }
+    b->tree_live = false; b->g_tree_live = false;
+    return TAFL_OK;
+}
+
 int tafl_batch_reset_fen(tafl_batch* b, const char* fen, uint8_t side) {
     if (!b || !fen) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     tafl_ctx* c = b->ctx;
     tafl_state st;
     int rc = tafl_state_from_fen(c, fen, side, &st);
     if (rc) return rc;
+    if ((rc = batch_write(b)) != TAFL_OK) return rc;
     HIPCHK(hipSetDevice(c->device));
     DISPATCH_NLW(c, {
         DState<NL> ds; state_from_abi<NL>(st, ds);
@@ -927,6 +1026,9 @@ int tafl_batch_upload(tafl_batch* b, const tafl_state* states, uint32_t first, u
     tafl_ctx* c = b->ctx;
     HIPCHK(hipSetDevice(c->device));
     const int Q = quads_of(c);
+    for (uint32_t i = 0; i < count; ++i)
+        if (states[i].side_len != c->n) return fail(TAFL_ERR_INVALID_ARG, "state.side_len differs from the context's side_len");
+    if (const int rc = batch_write(b)) return rc;
     std::vector<Quad> stage((size_t)Q * count);
     for (uint32_t i = 0; i < count; ++i) {
         if (states[i].side_len != c->n) return fail(TAFL_ERR_INVALID_ARG, "state.side_len differs from the context's side_len");
@@ -999,6 +1101,7 @@ int tafl_validate(tafl_batch* b, const tafl_play* plays, uint8_t* out_codes) {
 int tafl_step(tafl_batch* b, const tafl_play* plays, tafl_effects* out_effects) {
     if (!b || !plays) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    if (const int rc = batch_write(b)) return rc;
     HIPCHK(hipSetDevice(c->device));
     NEED(b->plays, sizeof(tafl_play) * n);
     if (out_effects) NEED(b->effects, sizeof(tafl_effects) * n);
@@ -1019,6 +1122,7 @@ int tafl_step(tafl_batch* b, const tafl_play* plays, tafl_effects* out_effects) 
 int tafl_step_kth(tafl_batch* b, const uint32_t* ranks, tafl_play* out_plays, tafl_effects* out_effects) {
     if (!b || !ranks) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    if (const int rc = batch_write(b)) return rc;
     HIPCHK(hipSetDevice(c->device));
     NEED(b->ranks, sizeof(uint32_t) * n); NEED(b->counts, sizeof(uint32_t) * 2 * (size_t)n);      // counts: chosen action and number of plays per game
     if (out_plays) NEED(b->out_plays, sizeof(tafl_play) * n);
@@ -1073,6 +1177,7 @@ int tafl_rollout(tafl_batch* b, uint64_t seed, uint32_t sim, uint32_t max_plies,
 int tafl_random_advance(tafl_batch* b, uint64_t seed, const uint32_t* plies, uint64_t game_id_base) {
     if (!b || !plies) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    if (const int rc = batch_write(b)) return rc;
     HIPCHK(hipSetDevice(c->device));
     NEED(b->plies, sizeof(uint32_t) * n);
     HIPCHK(hipMemcpyAsync(b->plies.p, plies, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream));
@@ -1089,6 +1194,7 @@ int tafl_mcts_reserve(tafl_batch* b, uint32_t max_sims) {
     tafl_ctx* c = b->ctx; const size_t n = b->n;
     HIPCHK(hipSetDevice(c->device));
     if (b->has_mem && b->reserved_sims >= max_sims) return TAFL_OK;
+    b->tree_live = false;                                    // (a larger arena starts empty)
     const size_t node_cap = (size_t)max_sims + 1, edge_cap = 4 * ((size_t)max_sims + 1);
     NEED(b->node_state, node_cap * n * arena_quads(c) * sizeof(Quad));
     NEED(b->hdr, node_cap * n * sizeof(NodeHdr));
@@ -1195,6 +1301,80 @@ static int mcts_enqueue_fused(tafl_batch* b, uint32_t rounds) {
 
 int tafl_mcts_wait(tafl_batch* b);
 
+// ---- subtree reuse: arena capacity (TAFL_MCTS_FLAG_KEEP_TREE) ---------------------------------------------------------------------------
+// the largest retained tree of the batch: out[0] = nodes, out[1] = edges (a 8-byte read-back)
+static int arena_max(tafl_batch* b, const uint32_t* node_top, const uint32_t* edge_top, uint32_t out[2]) {
+    tafl_ctx* c = b->ctx;
+    NEED(b->small, 64);
+    HIPCHK(hipMemsetAsync(b->small.p, 0, 8, c->stream));
+    hipLaunchKernelGGL(k_max2, dim3((b->n + 255) / 256), dim3(256), 0, c->stream, node_top, edge_top, b->n, (uint32_t*)b->small.p);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, b->small.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TAFL_OK;
+}
+// a device buffer grown to `bytes` with its first `keep` bytes kept (DevBuf::ensure drops the contents)
+static int grow_keep(DevBuf& d, size_t bytes, size_t keep, hipStream_t s) {
+    if (bytes <= d.cap) return TAFL_OK;
+    void* p = nullptr;
+    if (hipMalloc(&p, bytes) != hipSuccess) return fail(TAFL_ERR_OOM, "hipMalloc(arena growth) failed");
+    if (keep && (hipMemcpyAsync(p, d.p, keep, hipMemcpyDeviceToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)) {
+        (void)hipFree(p); return fail(TAFL_ERR_HIP, "arena growth: copy failed");
+    }
+    d.release(); d.p = p; d.cap = bytes;
+    return TAFL_OK;
+}
+// an edge arena [g * stride + e] of G games moved to a larger stride, contents kept (a strided copy)
+static int grow_stride(DevBuf& d, size_t elem, uint32_t G, uint32_t old_stride, uint32_t new_stride, hipStream_t s) {
+    if (new_stride <= old_stride) return TAFL_OK;
+    void* p = nullptr;
+    const size_t bytes = elem * new_stride * G;
+    if (hipMalloc(&p, bytes) != hipSuccess) return fail(TAFL_ERR_OOM, "hipMalloc(edge arena growth) failed");
+    if (hipMemcpy2DAsync(p, elem * new_stride, d.p, elem * old_stride, elem * old_stride, G, hipMemcpyDeviceToDevice, s) != hipSuccess ||
+        hipStreamSynchronize(s) != hipSuccess) {
+        (void)hipFree(p); return fail(TAFL_ERR_HIP, "edge arena growth: copy failed");
+    }
+    d.release(); d.p = p; d.cap = bytes;
+    return TAFL_OK;
+}
+// A search that continues the retained trees needs room for the largest of them plus its own growth: n_sims + 1 nodes, and edges for
+// 3 x the kept edges (a kept block that grows is copied once to twice its size before its new children pay for the next doubling) + the
+// 4 (n_sims + 1) of a fresh search.  The arena grows with its contents kept; nothing is ever pruned: a tree that cannot fit fails the call
+// before anything is launched.
+static int mcts_keep_capacity(tafl_batch* b, uint32_t n_sims) {
+    if (n_sims > 60000) return fail(TAFL_ERR_INVALID_ARG, "n_sims must be in 1..60000");
+    tafl_ctx* c = b->ctx; const size_t n = b->n;
+    uint32_t mx[2];
+    int rc = arena_max(b, b->mem.node_top, b->mem.edge_top, mx);
+    if (rc) return rc;
+    const unsigned long long nodes = (unsigned long long)mx[0] + n_sims + 1, edges = 3ull * mx[1] + 4ull * ((unsigned long long)n_sims + 1);
+    if (nodes > kMctsMaxNodes) return fail(TAFL_ERR_CAPACITY, "TAFL_MCTS_FLAG_KEEP_TREE: the retained tree and the new simulations exceed 2^20 nodes");
+    if (edges > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "TAFL_MCTS_FLAG_KEEP_TREE: the edge arena would exceed 2^32 edges per game");
+    const size_t aq = (size_t)arena_quads(c);
+    if (nodes > b->mem.node_cap) {
+        const size_t old = b->mem.node_cap;
+        // every pointer follows its buffer as soon as that buffer has moved: a later failure (TAFL_ERR_OOM) leaves a consistent arena
+        // of the old capacity with its tree intact
+        rc = grow_keep(b->node_state, nodes * n * aq * sizeof(Quad), old * n * aq * sizeof(Quad), c->stream);
+        b->mem.node_state = (Quad*)b->node_state.p;
+        if (rc != TAFL_OK) return rc;
+        rc = grow_keep(b->hdr, nodes * n * sizeof(NodeHdr), old * n * sizeof(NodeHdr), c->stream);
+        b->mem.hdr = (NodeHdr*)b->hdr.p;
+        if (rc != TAFL_OK) return rc;
+        b->mem.node_cap = (uint32_t)nodes;
+    }
+    if (edges > b->mem.edge_cap) {
+        rc = grow_stride(b->edges, sizeof(Edge), b->n, b->mem.edge_cap, (uint32_t)edges, c->stream);
+        b->mem.edges = (Edge*)b->edges.p;
+        if (rc != TAFL_OK) return rc;
+        b->mem.edge_cap = (uint32_t)edges;
+        b->edges_alt.release();
+    }
+    const uint32_t by_nodes = b->mem.node_cap - 1, by_edges = b->mem.edge_cap / 4 - 1;
+    b->reserved_sims = by_nodes < by_edges ? by_nodes : by_edges;
+    return TAFL_OK;
+}
+
 static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves = 0) {
     if (!b || !p) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     if (p->flags & ~(uint32_t)TAFL_MCTS_FLAGS_KNOWN) return fail(TAFL_ERR_UNSUPPORTED, "tafl_mcts_params.flags: unknown bits set");
@@ -1202,14 +1382,18 @@ static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id
     if (after && after->ctx->device != b->ctx->device) return fail(TAFL_ERR_INVALID_ARG, "tafl_mcts_run_async_after: the two batches live on different devices");
     int rc = TAFL_OK;
     if (b->plan.active && (rc = tafl_mcts_wait(b)) != TAFL_OK) return rc;       // one search per batch at a time
-    if ((rc = tafl_mcts_reserve(b, p->n_sims)) != TAFL_OK) return rc;
+    // TAFL_MCTS_FLAG_KEEP_TREE on a retained tree: the search continues it (a dropped tree: a fresh search)
+    const bool keep = (p->flags & TAFL_MCTS_FLAG_KEEP_TREE) && b->tree_live && b->has_mem;
+    if (keep) { if ((rc = mcts_keep_capacity(b, p->n_sims)) != TAFL_OK) return rc; }
+    else if ((rc = tafl_mcts_reserve(b, p->n_sims)) != TAFL_OK) return rc;
+    b->tree_live = false;
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     HIPCHK(hipSetDevice(c->device));
     SearchPlan& sp = b->plan;
     sp.p = *p; sp.base = game_id_base; sp.next_round = 0; sp.fused = false;
     sp.selfplay.n_moves = n_moves; sp.selfplay.moves_done = nullptr; sp.selfplay.start_round = nullptr; sp.selfplay.plays = nullptr;
     MctsMem& M = sp.M; M = b->mem;
-    M.node_cap = p->n_sims + 1; M.edge_cap = b->mem.edge_cap; M.flags = p->flags & TAFL_MCTS_FLAG_FPU_INF;
+    M.node_cap = keep ? b->mem.node_cap : p->n_sims + 1; M.edge_cap = b->mem.edge_cap; M.flags = p->flags & TAFL_MCTS_FLAG_FPU_INF;
     // tuning fields of `flags` (results never depend on them): pipeline and playout slots per game
     const uint32_t pipe = TAFL_MCTS_TUNE_PIPELINE_OF(p->flags);
     uint32_t slots = TAFL_MCTS_TUNE_SLOTS_OF(p->flags);
@@ -1263,7 +1447,8 @@ static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id
     unsigned long long* st = (unsigned long long*)b->stats.p;
     HIPCHK(hipMemsetAsync(st, 0, sizeof(unsigned long long) * ST_COUNT, s0));
     M.spec_k = fused ? slots : b->spec_k;
-    DISPATCH_ARENA(c, hipLaunchKernelGGL((k_mcts_init<NLS, WS, NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, s0, CC, b->soa, M));
+    if (keep) DISPATCH_ARENA(c, hipLaunchKernelGGL((k_mcts_keep_init<NLS, WS, NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, s0, CC, b->soa, M));
+    else DISPATCH_ARENA(c, hipLaunchKernelGGL((k_mcts_init<NLS, WS, NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, s0, CC, b->soa, M));
     b->ran = false; b->trace_rounds = 0;
     if (fused) {
         // Fused pipeline (k_mcts_fused): one wave owns 64 / K games for a whole chunk of rounds and leaves as soon as its games are done;
@@ -1360,6 +1545,7 @@ int tafl_mcts_wait(tafl_batch* b) {
         if (rc) return rc;
     }
     b->ran = true; b->stats_ok = true;
+    b->tree_live = sp.selfplay.n_moves == 0;                                 // (a self-play run leaves no tree for the current states)
     return TAFL_OK;
 }
 
@@ -1372,10 +1558,12 @@ int tafl_mcts_run(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_bas
 // barrier between the moves: a game starts its next search as soon as its own is done (SelfPlay, tafl_ops.hpp)
 int tafl_selfplay_run(tafl_batch* b, const tafl_mcts_params* p, uint32_t n_moves, uint64_t game_id_base, tafl_play* out_plays) {
     if (!b || !p || n_moves == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_run: bad argument");
+    if (p->flags & TAFL_MCTS_FLAG_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_run: TAFL_MCTS_FLAG_KEEP_TREE is not supported (no re-root inside a self-play run)");
     if ((unsigned long long)n_moves * p->n_sims + p->sim_offset > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_run: sim_offset + n_moves * n_sims exceeds 32 bits");
     int rc = mcts_begin(b, p, game_id_base, nullptr, n_moves);
     if (rc == TAFL_OK) rc = tafl_mcts_wait(b);
     b->ran = false;                                          // the trees belong to roots that have been played away from
+    b->tree_live = false; b->g_tree_live = false;
     if (rc) return rc;
     if (out_plays) {
         tafl_ctx* c = b->ctx;
@@ -1502,6 +1690,51 @@ int tafl_mcts_play_best(tafl_batch* b, tafl_play* out_plays, tafl_effects* out_e
     if (out_effects) HIPCHK(hipMemcpyAsync(out_effects, b->effects.p, sizeof(tafl_effects) * n, hipMemcpyDeviceToHost, c->stream));
     if (out_plays || out_effects) HIPCHK(hipStreamSynchronize(c->stream));
     b->ran = false;                                   // the tree belongs to the previous roots
+    b->tree_live = false; b->g_tree_live = false;
+    return TAFL_OK;
+}
+
+// play + re-root (TAFL_MCTS_FLAG_KEEP_TREE): k_mcts_advance writes every game's edges into the second edge arena, which then becomes the
+// arena.  A 4-byte read-back reports kept roots whose state differs from the batch state (an internal error; those games get fresh roots).
+int tafl_mcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "null batch");
+    int rc = TAFL_OK;
+    if (b->plan.active && (rc = tafl_mcts_wait(b)) != TAFL_OK) return rc;
+    const bool live = b->tree_live && b->has_mem;
+    if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_mcts_advance: actions == NULL needs a retained tree (run a search first)");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    HIPCHK(hipSetDevice(c->device));
+    if (!b->has_mem && (rc = tafl_mcts_reserve(b, 1)) != TAFL_OK) return rc;
+    NEED(b->edges_alt, b->edges.cap); NEED(b->idmap, (size_t)b->mem.node_cap * n * sizeof(uint32_t)); NEED(b->small, 64);
+    if (actions) { NEED(b->ranks, sizeof(uint32_t) * n); HIPCHK(hipMemcpyAsync(b->ranks.p, actions, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream)); }
+    if (out_plays) NEED(b->best_plays, sizeof(tafl_play) * n);
+    if (out_effects) NEED(b->effects, sizeof(tafl_effects) * n);
+    uint32_t* bad = (uint32_t*)b->small.p + 2;
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+    DISPATCH_ARENA(c, hipLaunchKernelGGL((k_mcts_advance<NLS, WS, NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, c->stream, batch_consts<NLS>(c), CC, b->mem, b->soa,
+                                       (Edge*)b->edges_alt.p, (uint32_t*)b->idmap.p, actions ? (const uint32_t*)b->ranks.p : nullptr, live ? 1 : 0, A,
+                                       out_plays ? (tafl_play*)b->best_plays.p : nullptr, out_effects ? (tafl_effects*)b->effects.p : nullptr, bad));
+    HIPCHK(hipGetLastError());
+    std::swap(b->edges, b->edges_alt);
+    b->mem.edges = (Edge*)b->edges.p;
+    b->tree_live = true; b->ran = true; b->g_tree_live = false;       // (the guided tree belongs to the states before the play)
+    uint32_t h_bad = 0;
+    HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream));
+    if (out_plays) HIPCHK(hipMemcpyAsync(out_plays, b->best_plays.p, sizeof(tafl_play) * n, hipMemcpyDeviceToHost, c->stream));
+    if (out_effects) HIPCHK(hipMemcpyAsync(out_effects, b->effects.p, sizeof(tafl_effects) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_bad) return fail(TAFL_ERR_HIP, "tafl_mcts_advance: a kept root differs from its new batch state (internal error; those games got fresh roots)");
+    return TAFL_OK;
+}
+
+int tafl_mcts_tree_nodes(tafl_batch* b, uint32_t* out) {
+    if (!b || !out) return fail(TAFL_ERR_INVALID_ARG, "null argument");
+    if (b->plan.active) { const int rc = tafl_mcts_wait(b); if (rc) return rc; }
+    if (!b->tree_live) { memset(out, 0, sizeof(uint32_t) * b->n); return TAFL_OK; }
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, b->mem.node_top, sizeof(uint32_t) * b->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
     return TAFL_OK;
 }
 
@@ -1620,12 +1853,102 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_root_dense(Consts<NL> C, G
     }
 }
 
+// subtree reuse in guided mode: keep-init and advance (k_mcts_keep_init / k_mcts_advance on the guided arena)
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_keep_init(Consts<NL> C, const Quad* soa, GuidedMem M) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    if (M.node_top[g] == 0) { DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st); Guided<NL, W>::init_game(M, g, st); }
+    else Guided<NL, W>::keep_init(M, g);
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_advance(Consts<NL> C, GuidedMem M, Quad* soa, GEdge* dst, uint32_t* idmap, const uint32_t* actions, int live,
+                                                              uint32_t A, tafl_play* out_plays, tafl_effects* eff, uint32_t* bad) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    const GNode h = M.hdr[g];
+    const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+    uint32_t a = actions ? actions[g] : TAFL_ACTION_NONE, child = 0;
+    if (live && h.expanded) {
+        uint32_t best = 0;
+        for (uint32_t j = 0; j < h.n_legal; ++j) {                  // ascending action order: the first maximum
+            const GEdge e = eb[j];
+            if (actions ? e.action == a : e.n > best) { best = e.n; child = e.child; a = e.action; if (actions) break; }
+        }
+    }
+    DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st);
+    tafl_play p; tafl_effects e;
+    const bool played = advance_play<NL, W>(C, st, a, A, p, e);
+    if (played) StateIO<NL>::store_soa(soa, M.G, g, st);
+    const bool alone = !played && (a == TAFL_ACTION_NONE || e.code == TAFL_PLAY_GAME_OVER);
+    if (live && alone) Guided<NL, W>::keep_edges(M, dst, g);
+    else {
+        bool fresh = !(live && played && child != 0);
+        if (!fresh) {
+            Guided<NL, W>::reroot(M, dst, idmap, g, child);
+            if (!same_state<NL>(M.node_state + (size_t)g * StateIO<NL>::QUADS, st)) { atomicAdd(bad, 1u); fresh = true; }
+        }
+        if (fresh) Guided<NL, W>::init_game(M, g, st);
+    }
+    if (out_plays) out_plays[g] = p;
+    if (eff) eff[g] = e;
+}
+
 extern "C" {
 
-int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) {
+int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) { return tafl_gmcts_begin_ex(b, max_sims, edges_per_node, 0); }
+
+// TAFL_GMCTS_KEEP_TREE on a retained tree: the arena grows (contents kept) to the largest kept tree + max_sims + 1 nodes and + (max_sims + 1)
+// x edges_per_node edges, and only the per-search fields are reset
+static int gmcts_begin_keep(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) {
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
+    GuidedMem& M = b->gmem;
+    uint32_t mx[2];
+    int rc = arena_max(b, M.node_top, M.edge_top, mx);
+    if (rc) return rc;
+    const unsigned long long nodes = (unsigned long long)mx[0] + max_sims + 1, ecap = (unsigned long long)mx[1] + ((unsigned long long)max_sims + 1) * edges_per_node;
+    if (nodes > 0xFFFFFFFFull || ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_begin_ex: the retained tree and the new simulations exceed the arena's index range");
+    if (nodes > M.node_cap) {
+        const size_t old = M.node_cap;
+        // (each pointer follows its buffer at once, as in mcts_keep_capacity)
+        rc = grow_keep(b->g_node_state, sizeof(Quad) * q * nodes * n, sizeof(Quad) * q * old * n, c->stream);
+        M.node_state = (Quad*)b->g_node_state.p;
+        if (rc != TAFL_OK) return rc;
+        rc = grow_keep(b->g_hdr, sizeof(GNode) * nodes * n, sizeof(GNode) * old * n, c->stream);
+        M.hdr = (GNode*)b->g_hdr.p;
+        if (rc != TAFL_OK) return rc;
+        rc = grow_keep(b->g_pedge, sizeof(uint32_t) * nodes * n, sizeof(uint32_t) * old * n, c->stream);
+        M.pedge = (uint32_t*)b->g_pedge.p;
+        if (rc != TAFL_OK) return rc;
+        M.node_cap = (uint32_t)nodes;
+    }
+    if (ecap > M.edge_cap) {
+        rc = grow_stride(b->g_edges, sizeof(GEdge), n, M.edge_cap, (uint32_t)ecap, c->stream);
+        M.edges = (GEdge*)b->g_edges.p;
+        if (rc != TAFL_OK) return rc;
+        M.edge_cap = (uint32_t)ecap;
+        b->g_edges_alt.release();
+    }
+    HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
+    DISPATCH_NLW(c, hipLaunchKernelGGL((k_gmcts_keep_init<NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, c->stream, CC, b->soa, M));
+    HIPCHK(hipGetLastError());
+    b->g_max_sims = max_sims;
+    return TAFL_OK;
+}
+
+int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, uint32_t flags) {
     if (!b || max_sims == 0 || edges_per_node == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_begin: bad argument");
+    if (flags & ~(uint32_t)TAFL_GMCTS_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: unknown flags");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
     HIPCHK(hipSetDevice(c->device));
+    if (flags & TAFL_GMCTS_KEEP_TREE) { if (b->plan.active) { const int rc = tafl_mcts_wait(b); if (rc) return rc; } }
+    if ((flags & TAFL_GMCTS_KEEP_TREE) && b->g_has && b->g_tree_live) {
+        b->g_tree_live = false;
+        const int rc = gmcts_begin_keep(b, max_sims, edges_per_node);
+        if (rc == TAFL_OK) b->g_tree_live = true;
+        return rc;
+    }
+    b->g_tree_live = false;
     const uint32_t node_cap = max_sims + 1;
     const unsigned long long ecap = (unsigned long long)node_cap * edges_per_node;
     if (ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_begin: edge arena too large");
@@ -1640,7 +1963,7 @@ int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) 
     HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
     DISPATCH_NLW(c, hipLaunchKernelGGL((k_gmcts_init<NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, c->stream, CC, b->soa, M));
     HIPCHK(hipGetLastError());
-    b->g_has = true; b->g_max_sims = max_sims;
+    b->g_has = true; b->g_max_sims = max_sims; b->g_tree_live = true;
     return TAFL_OK;
 }
 
@@ -1729,6 +2052,47 @@ int tafl_gmcts_policy_ex(tafl_batch* b, double temp, uint64_t tie_seed, uint64_t
     return gmcts_dense(b, nullptr, out, temp, out_is_device, tie_seed, game_id_base);
 }
 int tafl_gmcts_policy(tafl_batch* b, double temp, double* out, int out_is_device) { return tafl_gmcts_policy_ex(b, temp, 0, 0, out, out_is_device); }
+int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects) {
+    if (!b || !b->g_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: tafl_gmcts_begin first");
+    int rc = TAFL_OK;
+    if (b->plan.active && (rc = tafl_mcts_wait(b)) != TAFL_OK) return rc;
+    const bool live = b->g_tree_live;
+    if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: actions == NULL needs a retained tree");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    HIPCHK(hipSetDevice(c->device));
+    GuidedMem& M = b->gmem;
+    NEED(b->g_edges_alt, b->g_edges.cap); NEED(b->g_idmap, (size_t)M.node_cap * n * sizeof(uint32_t)); NEED(b->small, 64);
+    if (actions) { NEED(b->ranks, sizeof(uint32_t) * n); HIPCHK(hipMemcpyAsync(b->ranks.p, actions, sizeof(uint32_t) * n, hipMemcpyHostToDevice, c->stream)); }
+    if (out_plays) NEED(b->best_plays, sizeof(tafl_play) * n);
+    if (out_effects) NEED(b->effects, sizeof(tafl_effects) * n);
+    uint32_t* bad = (uint32_t*)b->small.p + 2;
+    HIPCHK(hipMemsetAsync(bad, 0, sizeof(uint32_t), c->stream));
+    DISPATCH_NLW(c, hipLaunchKernelGGL((k_gmcts_advance<NL, W>), dim3(grid_of(n)), dim3(TAFL_BLOCK), 0, c->stream, CC, M, b->soa, (GEdge*)b->g_edges_alt.p,
+                                       (uint32_t*)b->g_idmap.p, actions ? (const uint32_t*)b->ranks.p : nullptr, live ? 1 : 0, A,
+                                       out_plays ? (tafl_play*)b->best_plays.p : nullptr, out_effects ? (tafl_effects*)b->effects.p : nullptr, bad));
+    HIPCHK(hipGetLastError());
+    std::swap(b->g_edges, b->g_edges_alt);
+    M.edges = (GEdge*)b->g_edges.p;
+    b->g_tree_live = true; b->tree_live = false;                      // (the rollout-mode tree belongs to the states before the play)
+    uint32_t h_bad = 0;
+    HIPCHK(hipMemcpyAsync(&h_bad, bad, sizeof h_bad, hipMemcpyDeviceToHost, c->stream));
+    if (out_plays) HIPCHK(hipMemcpyAsync(out_plays, b->best_plays.p, sizeof(tafl_play) * n, hipMemcpyDeviceToHost, c->stream));
+    if (out_effects) HIPCHK(hipMemcpyAsync(out_effects, b->effects.p, sizeof(tafl_effects) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (h_bad) return fail(TAFL_ERR_HIP, "tafl_gmcts_advance: a kept root differs from its new batch state (internal error; those games got fresh roots)");
+    return TAFL_OK;
+}
+
+int tafl_gmcts_tree_nodes(tafl_batch* b, uint32_t* out) {
+    if (!b || !out) return fail(TAFL_ERR_INVALID_ARG, "null argument");
+    if (!b->g_has || !b->g_tree_live) { memset(out, 0, sizeof(uint32_t) * b->n); return TAFL_OK; }
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipMemcpyAsync(out, b->gmem.node_top, sizeof(uint32_t) * b->n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TAFL_OK;
+}
+
 int tafl_gmcts_get_stats(tafl_batch* b, tafl_gmcts_stats* out) {
     if (!b || !b->g_has || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_get_stats: bad argument");
     tafl_ctx* c = b->ctx;

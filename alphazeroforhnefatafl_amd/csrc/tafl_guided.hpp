@@ -209,6 +209,60 @@ struct Guided {
         M.sims_done[g] = sims;
     }
 
+    // ---- subtree reuse (TAFL_GMCTS_KEEP_TREE) -------------------------------------------------------------
+    // per-search fields of a retained tree (nodes, edges, priors and values stay)
+    static TAFL_HD void keep_init(const GuidedMem& M, uint32_t g) { M.leaf[g] = 0; M.kind[g] = 0; M.fault[g] = 0; M.sims_done[g] = 0; }
+    static constexpr uint32_t NO_NODE = 0xFFFFFFFFu;
+    // Node c (a child of the root) becomes the root of game g, as Ops::mcts_reroot: ids are decided by one upward sweep (a parent's id is
+    // lower than its children's), nodes move in place in ascending order, the edge blocks of the kept expanded nodes are written densely
+    // into the second arena `dst`.  pedge is stored relative to the parent's block between the two passes (the parent's old edge_base is
+    // gone once it has moved).
+    static TAFL_HD void reroot(const GuidedMem& M, GEdge* dst, uint32_t* idmap, uint32_t g, uint32_t c) {
+        const uint32_t top = M.node_top[g];
+        idmap[(size_t)c * M.G + g] = 0;
+        uint32_t cnt = 1;
+        for (uint32_t k = c + 1; k < top; ++k) {
+            const uint32_t p = M.hdr[(size_t)k * M.G + g].parent;
+            const bool keep = p >= c && p < k && idmap[(size_t)p * M.G + g] != NO_NODE;
+            idmap[(size_t)k * M.G + g] = keep ? cnt++ : NO_NODE;
+            if (keep) M.pedge[(size_t)k * M.G + g] -= M.hdr[(size_t)p * M.G + g].edge_base;
+        }
+        uint32_t etop = 0;
+        for (uint32_t k = c; k < top; ++k) {
+            const uint32_t nk = idmap[(size_t)k * M.G + g];
+            if (nk == NO_NODE) continue;
+            GNode h = M.hdr[(size_t)k * M.G + g];
+            const uint32_t rel = M.pedge[(size_t)k * M.G + g];
+            uint32_t nbase = 0;
+            if (h.expanded) {
+                const GEdge* src = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+                GEdge* de = &dst[(size_t)g * M.edge_cap + etop];
+                for (uint32_t j = 0; j < h.n_legal; ++j) {
+                    GEdge e = src[j];
+                    e.child = (e.child > k && e.child < top) ? idmap[(size_t)e.child * M.G + g] : 0u;
+                    de[j] = e;
+                }
+                nbase = etop; etop += h.n_legal;
+            }
+            uint32_t pe = 0;
+            if (k == c) h.parent = 0;
+            else { h.parent = idmap[(size_t)h.parent * M.G + g]; pe = M.hdr[(size_t)h.parent * M.G + g].edge_base + rel; }   // (the parent has moved already)
+            h.edge_base = nbase;
+            M.hdr[(size_t)nk * M.G + g] = h;
+            M.pedge[(size_t)nk * M.G + g] = pe;
+            if (nk != k) {
+                const Quad* s = M.node_state + ((size_t)k * M.G + g) * IO::QUADS;
+                Quad* d = M.node_state + ((size_t)nk * M.G + g) * IO::QUADS;
+                TAFL_UNROLL for (int q = 0; q < IO::QUADS; ++q) d[q] = s[q];
+            }
+        }
+        M.node_top[g] = cnt; M.edge_top[g] = etop;
+    }
+    static TAFL_HD void keep_edges(const GuidedMem& M, GEdge* dst, uint32_t g) {
+        const uint32_t n = M.edge_top[g];
+        for (uint32_t j = 0; j < n; ++j) dst[(size_t)g * M.edge_cap + j] = M.edges[(size_t)g * M.edge_cap + j];
+    }
+
     // visited root edges in ascending action order (mcts.py:40-41)
     static TAFL_HD uint32_t root_children(const GuidedMem& M, uint32_t g, tafl_root_child* out, uint32_t max_children) {
         const GNode h = M.hdr[g];

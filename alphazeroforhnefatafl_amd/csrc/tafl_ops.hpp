@@ -991,6 +991,59 @@ struct Ops {
         return 2;
     }
 
+    // ---- subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE) ------------------------------------------------------------
+    // The per-search fields of a retained tree: nodes, edges, node_top and edge_top stay, the pipeline state of the last search goes.  Slot
+    // references name nodes that a re-root renumbers; a playout is a function of its position, so clearing them costs no result.
+    static TAFL_HD void mcts_keep_init(const MctsMem& M, uint32_t g) {
+        M.leaf[g] = 0; M.kind[g] = 0; M.fault[g] = 0;
+        M.sim_next[g] = 0; M.sim_base[g] = 0; M.spec_pend[g] = (M.spec_k > 0 ? M.spec_k - 1 : 0u) << 16; M.spec_bias[g] = 0;
+        for (uint32_t j = 0; j < M.spec_k; ++j) M.spec_kind[(size_t)j * M.G + g] = 0;
+    }
+    static constexpr uint32_t NO_NODE = 0xFFFFFFFFu;
+    // Node c (a child of the root) becomes the root of game g; its subtree is kept, everything else is dropped.  A parent's id is always
+    // lower than its children's, so one upward sweep from c decides which nodes are kept (idmap[k * G + g]: new id or NO_NODE).  New ids
+    // are dense and keep the old order (new <= old), so the nodes move in place in ascending order.  The edge blocks do not follow node
+    // order (a block moves to edge_top when it grows), so the kept blocks are written densely into a second arena `dst`, each keeping its
+    // capacity, with their child ids renumbered.
+    static TAFL_HD void mcts_reroot(const MctsMem& M, Edge* dst, uint32_t* idmap, uint32_t g, uint32_t c) {
+        const uint32_t top = M.node_top[g];
+        idmap[(size_t)c * M.G + g] = 0;
+        uint32_t cnt = 1;
+        for (uint32_t k = c + 1; k < top; ++k) {
+            const uint32_t p = M.hdr[(size_t)k * M.G + g].parent;
+            const bool keep = p >= c && p < k && idmap[(size_t)p * M.G + g] != NO_NODE;
+            idmap[(size_t)k * M.G + g] = keep ? cnt++ : NO_NODE;
+        }
+        uint32_t etop = 0;
+        for (uint32_t k = c; k < top; ++k) {
+            const uint32_t nk = idmap[(size_t)k * M.G + g];
+            if (nk == NO_NODE) continue;
+            NodeHdr h = M.hdr[(size_t)k * M.G + g];
+            const Edge* src = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+            Edge* de = &dst[(size_t)g * M.edge_cap + etop];
+            for (uint32_t j = 0; j < h.m; ++j) {
+                Edge e = src[j];
+                e.child = (e.child > k && e.child < top) ? idmap[(size_t)e.child * M.G + g] : NO_NODE;
+                de[j] = e;
+            }
+            h.edge_base = etop; etop += h.cap;
+            if (k == c) { h.parent = 0; h.pslot = 0; h.mv_from = 0; h.mv_dir = 0; h.mv_dist = 0; }     // as mcts_init_game
+            else h.parent = idmap[(size_t)h.parent * M.G + g];
+            M.hdr[(size_t)nk * M.G + g] = h;
+            if (nk != k) {
+                const Quad* s = M.node_state + ((size_t)k * M.G + g) * IO::QUADS;
+                Quad* d = M.node_state + ((size_t)nk * M.G + g) * IO::QUADS;
+                TAFL_UNROLL for (int q = 0; q < IO::QUADS; ++q) d[q] = s[q];
+            }
+        }
+        M.node_top[g] = cnt; M.edge_top[g] = etop;
+    }
+    // game g's tree unchanged in the second edge arena (a game the re-root leaves alone)
+    static TAFL_HD void mcts_keep_edges(const MctsMem& M, Edge* dst, uint32_t g) {
+        const uint32_t n = M.edge_top[g];
+        if (n) copy_edges(&dst[(size_t)g * M.edge_cap], &M.edges[(size_t)g * M.edge_cap], n);
+    }
+
     // root statistics (mcts.py:40-41): visited root children in canonical order
     static TAFL_HD uint32_t mcts_root_children(const MctsMem& M, uint32_t g, const K& C, tafl_root_child* out, uint32_t max_children) {
         const NodeHdr h = M.hdr[g];

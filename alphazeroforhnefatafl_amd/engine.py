@@ -175,19 +175,20 @@ class GameBatch:
         check(lib().tafl_mcts_reserve(self._h, max_sims))
 
     def mcts_run(self, n_sims: int, c_puct: float, seed: int, max_rollout_plies: int, game_id_base: int = 0,
-                 sim_offset: int = 0, flags: int = 0):
+                 sim_offset: int = 0, flags: int = 0, keep: bool = False):
         """`for i in range(numMCTSSims): self.search(canonicalBoard)` of MCTS.getActionProb (src/mcts.py:37-38) for every game.
-        `flags`: abi.MCTS_FLAG_* semantics bits | abi.mcts_tune(pipeline, slots) execution tuning (never changes results)."""
-        p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags)
+        `flags`: abi.MCTS_FLAG_* semantics bits | abi.mcts_tune(pipeline, slots) execution tuning (never changes results).
+        `keep`: continue the retained tree (abi.MCTS_FLAG_KEEP_TREE): the reference's MCTS object whose tables persist across calls."""
+        p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags | (abi.MCTS_FLAG_KEEP_TREE if keep else 0))
         check(lib().tafl_mcts_run(self._h, C.byref(p), game_id_base))
 
     def mcts_run_async(self, n_sims: int, c_puct: float, seed: int, max_rollout_plies: int, game_id_base: int = 0,
-                       sim_offset: int = 0, flags: int = 0, after: "GameBatch | None" = None):
+                       sim_offset: int = 0, flags: int = 0, after: "GameBatch | None" = None, keep: bool = False):
         """The same search, enqueued on the batch's own streams without blocking the host (tafl_mcts_run_async): the search of another batch,
         a network, or the bookkeeping of the previous move run beside it.  `after`: hold this search back until that batch's search in
         flight is half-way through (two half-size batches started this way stay half a search apart, so that the nearly empty last rounds
         of one run under the full rounds of the other).  Join with mcts_wait(); every reader of the results joins by itself."""
-        p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags)
+        p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags | (abi.MCTS_FLAG_KEEP_TREE if keep else 0))
         if after is None:
             check(lib().tafl_mcts_run_async(self._h, C.byref(p), game_id_base))
         else:
@@ -255,8 +256,12 @@ class GameBatch:
         return out
 
     # -- guided MCTS: the caller's network is nnet.predict (src/mcts.py:85) --------------------------------------------
-    def gmcts_begin(self, max_sims: int, edges_per_node: int = 256):
-        check(lib().tafl_gmcts_begin(self._h, max_sims, edges_per_node))
+    def gmcts_begin(self, max_sims: int, edges_per_node: int = 256, keep: bool = False):
+        """`keep`: continue the retained guided tree (abi.GMCTS_KEEP_TREE): kept nodes keep their priors and values."""
+        if keep:
+            check(lib().tafl_gmcts_begin_ex(self._h, max_sims, edges_per_node, abi.GMCTS_KEEP_TREE))
+        else:
+            check(lib().tafl_gmcts_begin(self._h, max_sims, edges_per_node))
 
     def gmcts_step(self, priors=None, values=None, c_puct: float = 1.0, n_sims: int = 64, device: bool = False, want_waiting: bool = True) -> int:
         """Expand the waiting leaves with (priors float32 [n, action_size], values float32 [n]) and select the next ones.
@@ -319,3 +324,39 @@ class GameBatch:
         visits = (C.c_uint32 * self.n)()
         check(lib().tafl_mcts_best_play(self._h, plays, visits))
         return plays, visits
+
+    # -- subtree reuse (include/taflhip.h tafl_mcts_advance) ------------------------------------------------------------
+    def _advance(self, fn, actions, want_results: bool):
+        acts = None
+        if actions is not None:
+            actions = list(actions)
+            if len(actions) != self.n:
+                raise ValueError(f"advance: {len(actions)} actions for {self.n} games (use abi.ACTION_NONE to leave a game alone)")
+            acts = (C.c_uint32 * self.n)(*[int(a) & 0xFFFFFFFF for a in actions])
+        if not want_results:
+            check(fn(self._h, acts, None, None))
+            return None
+        plays, eff = (TaflPlay * self.n)(), (TaflEffects * self.n)()
+        check(fn(self._h, acts, plays, eff))
+        return plays, eff
+
+    def mcts_advance(self, actions=None, want_results: bool = True):
+        """Play actions[g] (dense action index; abi.ACTION_NONE leaves the game alone; None: the most visited root child) and make that
+        child the root of the retained tree (tafl_mcts_advance).  Returns (plays, effects) unless want_results is False."""
+        return self._advance(lib().tafl_mcts_advance, actions, want_results)
+
+    def gmcts_advance(self, actions=None, want_results: bool = True):
+        """tafl_gmcts_advance: mcts_advance on the guided tree."""
+        return self._advance(lib().tafl_gmcts_advance, actions, want_results)
+
+    def mcts_tree_nodes(self):
+        """Nodes per game in the retained rollout-mode tree (0: none)."""
+        out = (C.c_uint32 * self.n)()
+        check(lib().tafl_mcts_tree_nodes(self._h, out))
+        return out
+
+    def gmcts_tree_nodes(self):
+        """Nodes per game in the retained guided tree (0: none)."""
+        out = (C.c_uint32 * self.n)()
+        check(lib().tafl_gmcts_tree_nodes(self._h, out))
+        return out

@@ -5,6 +5,10 @@ the batch on the GPU (select / expand / random-rollout / backup as lock-step HIP
 policy vectors of src/mcts.py:40-53.  Without a network, `predict` is the random-rollout mode of SURVEY.md §8a (uniform priors over legal plays + the value of
 one seeded random playout).  With `nnet`, `predict` is the caller's network evaluated for the whole batch at once
 (`GuidedMCTS`, include/taflhip.h "guided MCTS"): nnet.predict_batch(boards, sides, waiting) -> (priors, values).
+
+With `keep_tree=True` the object keeps its tables across calls as the reference's does: a second getActionProb adds numMCTSSims
+simulations to the first, and `advance(actions)` plays a move and keeps the played child's subtree (include/taflhip.h
+tafl_mcts_advance).  The default (False) starts every search from an empty root.
 """
 from __future__ import annotations
 
@@ -23,16 +27,23 @@ class MCTSArgs:
 
 
 class MCTS:
-    def __init__(self, batch: GameBatch, args: MCTSArgs):
+    def __init__(self, batch: GameBatch, args: MCTSArgs, keep_tree: bool = False):
         self.batch = batch
         self.args = args
+        self.keep_tree = keep_tree
         self._ran = False
 
     def search_all(self):
         """`for i in range(numMCTSSims): self.search(canonicalBoard)` (src/mcts.py:37-38) for every game."""
         a = self.args
-        self.batch.mcts_run(a.numMCTSSims, a.cpuct, a.seed, a.max_rollout_plies, a.game_id_base)
+        self.batch.mcts_run(a.numMCTSSims, a.cpuct, a.seed, a.max_rollout_plies, a.game_id_base, keep=self.keep_tree)
         self._ran = True
+
+    def advance(self, actions=None):
+        """Play actions[g] in every game (None: the most visited root child) and keep the played child's subtree (keep_tree=True)."""
+        if not self.keep_tree:
+            raise ValueError("MCTS.advance needs keep_tree=True")
+        return self.batch.mcts_advance(actions)
 
     def getActionProb(self, temp: float = 1.0):
         """src/mcts.py:28-53.  Returns a flat ctypes array [n_games * action_size] of float64.
@@ -62,15 +73,16 @@ class GuidedMCTS:
     (`buffers=(boards_ptr, sides_ptr, waiting_ptr)`) and the outputs are device pointers too: nothing crosses PCIe.
     """
 
-    def __init__(self, batch: GameBatch, nnet, args: MCTSArgs, edges_per_node: int = 256, device: bool = False, buffers=None):
-        self.batch, self.nnet, self.args = batch, nnet, args
+    def __init__(self, batch: GameBatch, nnet, args: MCTSArgs, edges_per_node: int = 256, device: bool = False, buffers=None,
+                 keep_tree: bool = False):
+        self.batch, self.nnet, self.args, self.keep_tree = batch, nnet, args, keep_tree
         self.edges_per_node, self.device, self.buffers = edges_per_node, device, buffers
         self.rounds = 0
         self._ran = False
 
     def search_all(self):
         a, b = self.args, self.batch
-        b.gmcts_begin(a.numMCTSSims, self.edges_per_node)
+        b.gmcts_begin(a.numMCTSSims, self.edges_per_node, keep=self.keep_tree)
         waiting = b.gmcts_step(None, None, a.cpuct, a.numMCTSSims)
         while waiting:
             if self.device:
@@ -91,3 +103,9 @@ class GuidedMCTS:
         if not self._ran:
             self.search_all()
         return self.batch.gmcts_root_children(max_children)
+
+    def advance(self, actions=None):
+        """Play actions[g] in every game (None: the most visited root child) and keep the played child's subtree (keep_tree=True)."""
+        if not self.keep_tree:
+            raise ValueError("GuidedMCTS.advance needs keep_tree=True")
+        return self.batch.gmcts_advance(actions)

@@ -209,6 +209,13 @@ typedef struct tafl_mcts_params {
  *     action index; the sketch does not compile and leaves the order of `valid_actions` undefined).  Everything else is src/mcts.py.
  *     This mode is pinned by the oracle only (no reference implementation can run it). */
 #define TAFL_MCTS_FLAG_FPU_INF 0x1u
+/*   TAFL_MCTS_FLAG_KEEP_TREE  continue the batch's retained tree instead of starting from an empty root: the reference's MCTS object with
+ *     tables that persist across getActionProb calls (src/mcts.py:20-26).  A search of S followed by a keep-search of S' gives the result of
+ *     one search of S + S', bit for bit; after tafl_mcts_advance the search starts from the played child's statistics.  Any other change to
+ *     the batch (upload, reset_fen, step, step_kth, random_advance, a search without this bit, play_best, selfplay_run) drops the tree, and
+ *     a keep-search on a dropped tree is a fresh search.  A kept leaf keeps the playout value it got in the search that expanded it; new
+ *     leaves use this run's seed, sim_offset and ply cap.  tafl_selfplay_run rejects the bit. */
+#define TAFL_MCTS_FLAG_KEEP_TREE 0x2u
 /* tuning fields of tafl_mcts_params.flags: they choose HOW the same search is executed and never change its results
  * (tests/test_gpu_parity.py::test_mcts_pipelines_agree).
  *   bits 4-7   pipeline: 0 default (64-bit boards: fused; wider boards: two kernels per round, tree phase + playouts over dense work
@@ -227,7 +234,7 @@ typedef struct tafl_mcts_params {
 #define TAFL_MCTS_TUNE_SHARE_OF(f) (((f) >> 16) & 15u)
 #define TAFL_MCTS_TUNE_PIPELINE_OF(f) (((f) >> 4) & 15u)
 #define TAFL_MCTS_TUNE_SLOTS_OF(f) (((f) >> 8) & 15u)
-#define TAFL_MCTS_FLAGS_KNOWN 0x000FFFF1u
+#define TAFL_MCTS_FLAGS_KNOWN 0x000FFFF3u
 
 typedef struct tafl_mcts_stats {
     uint64_t sims;             /* simulations executed (all games) */
@@ -361,6 +368,19 @@ int tafl_mcts_play_best(tafl_batch* b, tafl_play* out_plays, tafl_effects* out_e
  * synchronous searches ends every search in a tail of nearly empty rounds).  Games that end stop searching; out_plays[m * n + g] (may be
  * NULL) is the play game g made at move m, all-zero once its game was over.  tafl_mcts_get_stats afterwards covers all searches. */
 int tafl_selfplay_run(tafl_batch* b, const tafl_mcts_params* params, uint32_t n_moves, uint64_t game_id_base, tafl_play* out_plays);
+/* Subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE).  tafl_mcts_advance plays actions[g] (a dense action index, tafl_action_encode order) in game g
+ * with do_valid_play, exactly as tafl_step, and makes the child (root, action) the root of the retained tree: every statistic below it is
+ * kept, its siblings are dropped.  actions == NULL: the most visited root child, first maximum (tafl_mcts_play_best, but the tree is kept).
+ * A game with nothing to play is left alone, its tree kept, its play all-zero and effects.code = TAFL_PLAY_GAME_OVER, as play_best
+ * reports it: a TAFL_ACTION_NONE entry (even in an ongoing game), a game that is over, or (actions == NULL) a root without a visited
+ * child.  A child that was never visited gives a fresh root.  An illegal action (action >= tafl_action_size: TAFL_PLAY_OUT_OF_BOUNDS)
+ * leaves the state unchanged, drops the game's tree (a fresh root) and reports the validation code.
+ * After an advance the readers (root_children, root_visits, policy*, best_play) report the kept root.  out_* may be NULL.  A search in
+ * flight is joined first.
+ * tafl_mcts_tree_nodes: nodes per game in the retained tree (out[n]) - the states of the reference's Es table below the root. */
+#define TAFL_ACTION_NONE 0xFFFFFFFFu
+int tafl_mcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects);
+int tafl_mcts_tree_nodes(tafl_batch* b, uint32_t* out);
 
 /* ---- training-tensor writers (the step right after the hot path) ------------------------------
  * tafl_encode_boards: board_to_matrix (game/main.rs:55-83) for every game: uint8 [n * side_len * side_len], row-major;
@@ -402,6 +422,14 @@ int tafl_gmcts_root_visits(tafl_batch* b, uint32_t* out, int out_is_device);
 int tafl_gmcts_policy(tafl_batch* b, double temp, double* out, int out_is_device);
 int tafl_gmcts_policy_ex(tafl_batch* b, double temp, uint64_t tie_seed, uint64_t game_id_base, double* out, int out_is_device);
 int tafl_gmcts_get_stats(tafl_batch* b, tafl_gmcts_stats* out);
+/* Subtree reuse in guided mode: tafl_gmcts_begin_ex(..., TAFL_GMCTS_KEEP_TREE) continues the retained tree (priors and values of kept nodes
+ * stay; only new leaves wait for predict(), and stats.predicts counts only those), growing the arena by max_sims + 1 nodes beyond the kept
+ * ones while keeping its contents; without the bit it is tafl_gmcts_begin.  tafl_gmcts_advance / tafl_gmcts_tree_nodes: the contract of
+ * tafl_mcts_advance / tafl_mcts_tree_nodes on the guided tree.  The mutators listed at TAFL_MCTS_FLAG_KEEP_TREE and tafl_gmcts_begin drop it. */
+#define TAFL_GMCTS_KEEP_TREE 0x1u
+int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, uint32_t flags);
+int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects);
+int tafl_gmcts_tree_nodes(tafl_batch* b, uint32_t* out);
 
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
