@@ -1189,13 +1189,44 @@ int tafl_random_advance(tafl_batch* b, uint64_t seed, const uint32_t* plies, uin
 }
 
 // ---- MCTS ----------------------------------------------------------------------------------------------
-int tafl_mcts_reserve(tafl_batch* b, uint32_t max_sims) {
+static int grow_keep(DevBuf& d, size_t bytes, size_t keep, hipStream_t s);
+static int grow_stride(DevBuf& d, size_t elem, uint32_t G, uint32_t old_stride, uint32_t new_stride, hipStream_t s);
+
+// keep_tree: the caller may still read (or continue) the last search's tree; a search that starts afresh passes false
+static int mcts_reserve(tafl_batch* b, uint32_t max_sims, bool keep_tree) {
     if (!b || max_sims == 0 || max_sims > 60000) return fail(TAFL_ERR_INVALID_ARG, "max_sims must be in 1..60000");
     tafl_ctx* c = b->ctx; const size_t n = b->n;
     HIPCHK(hipSetDevice(c->device));
     if (b->has_mem && b->reserved_sims >= max_sims) return TAFL_OK;
-    b->tree_live = false;                                    // (a larger arena starts empty)
+    // growing frees the arena a search in flight runs on (its plan keeps its own copy of the pointers): join it first
+    if (b->plan.active) { const int rc = tafl_mcts_wait(b); if (rc) return rc; }
     const size_t node_cap = (size_t)max_sims + 1, edge_cap = 4 * ((size_t)max_sims + 1);
+    if (keep_tree && b->has_mem && (b->ran || b->tree_live)) {
+        // the last search's tree moves with the arena (its readers stay valid, a retained tree stays retained): the node arrays are
+        // node-major, so their contents are a prefix of the larger ones; the edge arena gets a larger per-game stride
+        const size_t aq = (size_t)arena_quads(c), old = b->mem.node_cap;
+        int rc = TAFL_OK;
+        if (node_cap > old) {
+            rc = grow_keep(b->node_state, node_cap * n * aq * sizeof(Quad), old * n * aq * sizeof(Quad), c->stream);
+            b->mem.node_state = (Quad*)b->node_state.p;
+            if (rc != TAFL_OK) return rc;
+            rc = grow_keep(b->hdr, node_cap * n * sizeof(NodeHdr), old * n * sizeof(NodeHdr), c->stream);
+            b->mem.hdr = (NodeHdr*)b->hdr.p;
+            if (rc != TAFL_OK) return rc;
+            b->mem.node_cap = (uint32_t)node_cap;
+        }
+        if (edge_cap > b->mem.edge_cap) {
+            rc = grow_stride(b->edges, sizeof(Edge), b->n, b->mem.edge_cap, (uint32_t)edge_cap, c->stream);
+            b->mem.edges = (Edge*)b->edges.p;
+            if (rc != TAFL_OK) return rc;
+            b->mem.edge_cap = (uint32_t)edge_cap;
+            b->edges_alt.release();
+        }
+        const uint32_t by_nodes = b->mem.node_cap - 1, by_edges = b->mem.edge_cap / 4 - 1;
+        b->reserved_sims = by_nodes < by_edges ? by_nodes : by_edges;
+        return TAFL_OK;
+    }
+    b->tree_live = false;
     NEED(b->node_state, node_cap * n * arena_quads(c) * sizeof(Quad));
     NEED(b->hdr, node_cap * n * sizeof(NodeHdr));
     NEED(b->edges, edge_cap * n * sizeof(Edge));
@@ -1219,6 +1250,7 @@ int tafl_mcts_reserve(tafl_batch* b, uint32_t max_sims) {
     b->has_mem = true; b->reserved_sims = max_sims;
     return TAFL_OK;
 }
+int tafl_mcts_reserve(tafl_batch* b, uint32_t max_sims) { return mcts_reserve(b, max_sims, true); }
 
 // ---- the search driver -------------------------------------------------------------------------------------------------------------
 // tafl_mcts_run_async enqueues a whole search - the planned rounds plus the rounds its stragglers usually need - on the batch's own
@@ -1375,7 +1407,7 @@ static int mcts_keep_capacity(tafl_batch* b, uint32_t n_sims) {
     return TAFL_OK;
 }
 
-static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves = 0) {
+static int mcts_begin_enqueue(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves) {
     if (!b || !p) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     if (p->flags & ~(uint32_t)TAFL_MCTS_FLAGS_KNOWN) return fail(TAFL_ERR_UNSUPPORTED, "tafl_mcts_params.flags: unknown bits set");
     if (p->n_sims == 0) return fail(TAFL_ERR_INVALID_ARG, "n_sims must be > 0");
@@ -1385,7 +1417,7 @@ static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id
     // TAFL_MCTS_FLAG_KEEP_TREE on a retained tree: the search continues it (a dropped tree: a fresh search)
     const bool keep = (p->flags & TAFL_MCTS_FLAG_KEEP_TREE) && b->tree_live && b->has_mem;
     if (keep) { if ((rc = mcts_keep_capacity(b, p->n_sims)) != TAFL_OK) return rc; }
-    else if ((rc = tafl_mcts_reserve(b, p->n_sims)) != TAFL_OK) return rc;
+    else if ((rc = mcts_reserve(b, p->n_sims, false)) != TAFL_OK) return rc;
     b->tree_live = false;
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     HIPCHK(hipSetDevice(c->device));
@@ -1523,6 +1555,20 @@ static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id
     return TAFL_OK;
 }
 
+// the launches of a search that is not in flight (any more) must not outlive the call that gave it up: nobody would join them
+static void search_streams_drain(tafl_batch* b) {
+    for (uint32_t k = 0; k < b->n_sstreams; ++k) (void)hipStreamSynchronize(b->sstream[k]);
+}
+// A failing return of mcts_begin_enqueue leaves plan.active == false, whatever it had enqueued by then (the stats memset, the init kernel,
+// the control block copy, rounds on every partition's stream): the streams are drained before the error is reported, so that no launch
+// runs on while the caller frees, grows or rewrites what it reads.  (A failure BEFORE the join of an earlier search leaves that search
+// in flight and active: it is joined like any other.)
+static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves = 0) {
+    const int rc = mcts_begin_enqueue(b, p, game_id_base, after, n_moves);
+    if (rc != TAFL_OK && b && !b->plan.active) search_streams_drain(b);
+    return rc;
+}
+
 int tafl_mcts_run_async(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base) { return mcts_begin(b, p, game_id_base, nullptr); }
 int tafl_mcts_run_async_after(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* other) { return mcts_begin(b, p, game_id_base, other); }
 
@@ -1542,7 +1588,7 @@ int tafl_mcts_wait(tafl_batch* b) {
         if (sp.fused) return fail(TAFL_ERR_HIP, "tafl_mcts_wait: the fused search ended with unfinished games");
         // stragglers: a few more rounds, then look again (a round of a nearly finished batch is a lone wave per partition)
         const int rc = mcts_enqueue_rounds(b, sp.planned >= 32 ? 4u : 2u, false);
-        if (rc) return rc;
+        if (rc) { search_streams_drain(b); return rc; }
     }
     b->ran = true; b->stats_ok = true;
     b->tree_live = sp.selfplay.n_moves == 0;                                 // (a self-play run leaves no tree for the current states)

@@ -335,6 +335,9 @@ int tafl_random_advance(tafl_batch* b, uint64_t seed, const uint32_t* plies, uin
  *     one-hot on the FIRST maximum — the reference draws uniformly among maxima with np.random,
  *     the deterministic choice is documented in DESIGN.md); out[n * tafl_action_size] float64.
  *   tafl_mcts_best_play: max-visit root child (src/mcts.rs:216-227), first maximum.
+ * tafl_mcts_reserve sizes the arena for searches of up to max_sims simulations ahead of time (tafl_mcts_run grows it by itself).  A
+ * search in flight is joined first; the tree of the last search moves into the larger arena, so its readers (and a retained tree)
+ * stay valid after the call.
  */
 int tafl_mcts_reserve(tafl_batch* b, uint32_t max_sims);
 int tafl_mcts_run(tafl_batch* b, const tafl_mcts_params* params, uint64_t game_id_base);
@@ -348,7 +351,8 @@ int tafl_mcts_run(tafl_batch* b, const tafl_mcts_params* params, uint64_t game_i
  * kept busy by another batch's full rounds.  tafl_mcts_run_async_after(b, ..., other) additionally holds b's search back until `other`'s
  * search in flight is half-way through its planned rounds (no effect if `other` has none): two half-size batches started this way stay
  * half a search apart, the steady state of a self-play loop `wait(A); play(A); run_async(A); wait(B); play(B); run_async(B)`.
- * The batch must not be modified (upload, step, reset) between run_async and wait. */
+ * A call that writes the batch states between run_async and wait (upload, reset_fen, step, step_kth, random_advance, mcts_play_best,
+ * mcts_advance) joins the search first, as tafl_mcts_reserve does: the order {run_async; call} gives what {run; call} gives. */
 int tafl_mcts_run_async(tafl_batch* b, const tafl_mcts_params* params, uint64_t game_id_base);
 int tafl_mcts_run_async_after(tafl_batch* b, const tafl_mcts_params* params, uint64_t game_id_base, tafl_batch* other);
 int tafl_mcts_wait(tafl_batch* b);

@@ -406,3 +406,115 @@ def random_ruleset(rng: random.Random) -> abi.Ruleset:
         starting_side=abi.ATTACKER, enclosure_win=rng.randrange(3),
         repetition_rule=None if rng.random() < 0.3 else (rng.randrange(1, 4), rng.random() < 0.5),
         draw_on_no_plays=rng.random() < 0.5, linnaean_capture=rng.random() < 0.5)
+
+
+# ---- whole-batch comparisons of root children (tests at the benchmark's own sizes) -------------------------------------------------
+
+def root_child_dtype():
+    """TaflRootChild as a numpy structured dtype (the play's four bytes as one word, Q as its float64 BITS: comparisons are bit-exact)."""
+    import numpy as np
+    from alphazeroforhnefatafl_amd.abi import TaflRootChild as T
+    return np.dtype({"names": ["play", "action", "visits", "qbits"], "formats": ["<u4", "<u4", "<u4", "<u8"],
+                     "offsets": [T.play.offset, T.action.offset, T.visits.offset, T.q.offset], "itemsize": C.sizeof(T)})
+
+
+def children_view(kids, cnt, n, width):
+    """(records [n, width], counts [n]) over the buffers mcts_root_children / gmcts_root_children / oracle.batch_mcts returned (no copy)."""
+    import numpy as np
+    return np.frombuffer(kids, dtype=root_child_dtype()).reshape(n, width), np.frombuffer(cnt, dtype=np.uint32)
+
+
+def first_children_diff(rec_a, cnt_a, rec_b, cnt_b):
+    """First game whose visited root children (count, then play / action / visits / Q bits of the entries below the count) differ
+    between two results of the same batch, or -1.  Entries at or beyond a game's count are ignored."""
+    import numpy as np
+    bad = cnt_a != cnt_b
+    used = np.arange(rec_a.shape[1], dtype=np.uint32)[None, :] < np.minimum(cnt_a, cnt_b)[:, None]
+    for f in ("play", "action", "visits", "qbits"):
+        bad |= ((rec_a[f] != rec_b[f]) & used).any(axis=1)
+    idx = np.flatnonzero(bad)
+    return int(idx[0]) if idx.size else -1
+
+
+def children_of(rec, cnt, g):
+    """[(action, visits, float(q).hex())] of game g: what the per-id oracle comparisons of the GPU tests compare."""
+    import numpy as np
+    k = int(cnt[g])
+    q = rec["qbits"][g, :k].copy().view(np.float64)
+    return [(int(rec["action"][g, j]), int(rec["visits"][g, j]), float(q[j]).hex()) for j in range(k)]
+
+
+def root_visit_sums(rec, cnt):
+    """Sum of the visits of the visited root children, per game."""
+    import numpy as np
+    used = np.arange(rec.shape[1], dtype=np.uint32)[None, :] < cnt[:, None]
+    return np.where(used, rec["visits"], 0).sum(axis=1, dtype=np.int64)
+
+
+def state_field(states, n, name):
+    """One byte-sized field of a TaflState array as a numpy vector [n] (status, side_to_play ...)."""
+    import numpy as np
+    return np.frombuffer(states, dtype=np.uint8).reshape(-1, C.sizeof(TaflState))[:n, getattr(TaflState, name).offset]
+
+
+def search_partitions(n, parts, block=64):
+    """[(g0, g1)] of the stream partitions a two-kernel search of n games is cut into: the rule of mcts_begin (tafl_capi.hip): the
+    batch's waves of `block` games are dealt out in order, the first `waves % parts` partitions get one more."""
+    waves = (n + block - 1) // block
+    parts = max(1, min(parts, waves))
+    per, extra = divmod(waves, parts)
+    out, w0 = [], 0
+    for k in range(parts):
+        wk = per + (1 if k < extra else 0)
+        out.append((w0 * block, min((w0 + wk) * block, n)))
+        w0 += wk
+    return out
+
+
+def default_search_parts(n, fused):
+    """Partitions of a search with default tuning flags (mcts_begin): two from 8 192 games on, one for the fused kernel."""
+    return 2 if (not fused and n >= 8192) else 1
+
+
+def boundary_ids(n, parts):
+    """0, 63, 64, n - 1 and, for every partition boundary, the last game of the partition and the first of the next."""
+    ids = {0, 63, 64, n - 1}
+    for (_g0, g1) in search_partitions(n, parts)[:-1]:
+        ids.update((g1 - 1, g1))
+    return sorted(i for i in ids if 0 <= i < n)
+
+
+def children_block_digests(rec, cnt, first_block=0, n_blocks=None, block=64):
+    """SHA-256 per block of `block` consecutive games over the packed records of their visited root children: per game the count
+    (uint32 LE), then per child action (uint32 LE), visits (uint32 LE), Q bits (uint64 LE).  rec / cnt: children_view of the games
+    first_block * block ... (local index 0 = the first game of first_block)."""
+    import hashlib
+    import numpy as np
+    packed = np.dtype([("a", "<u4"), ("v", "<u4"), ("q", "<u8")])
+    n = len(cnt)
+    n_blocks = (n + block - 1) // block if n_blocks is None else n_blocks
+    out = []
+    for blk in range(n_blocks):
+        h = hashlib.sha256()
+        for g in range(blk * block, min((blk + 1) * block, n)):
+            k = int(cnt[g])
+            p = np.empty(k, dtype=packed)
+            p["a"], p["v"], p["q"] = rec["action"][g, :k], rec["visits"][g, :k], rec["qbits"][g, :k]
+            h.update(np.uint32(k).tobytes() + p.tobytes())
+        out.append(h.hexdigest())
+    return out
+
+
+def oracle_children_parallel(oracle_mod, logic, word_bits, params, jobs, max_children=256, workers=16):
+    """oracle.batch_mcts on single games, side by side on host threads (ctypes releases the GIL inside the C call).
+    jobs: [(key, TaflState, global game id)] -> {key: [(action, visits, q.hex())]}."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    def one(job):
+        key, st, gid = job
+        arr = (TaflState * 1)(st)
+        ok, on, _ = oracle_mod.batch_mcts(logic, arr, 1, word_bits, params, gid, max_children)
+        return key, [(ok[j].action, ok[j].visits, float(ok[j].q).hex()) for j in range(on[0])]
+
+    with ThreadPoolExecutor(max_workers=max(1, min(workers, 16, len(jobs)))) as ex:
+        return dict(ex.map(one, jobs))
