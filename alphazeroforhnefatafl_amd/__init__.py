@@ -6,17 +6,21 @@ thousands of concurrent games) as hand-written HIP kernels behind a C-ABI (inclu
 from . import abi
 from .abi import Ruleset, boards, rules
 
-__all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame"]
+__all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples",
+           "play_episodes"]
 
 
 def __getattr__(name):
     # engine/mcts load libtaflhip.so (fails loudly if it is missing); abi is importable without it
-    if name in ("BatchedGameLogic", "GameBatch"):
+    if name in ("BatchedGameLogic", "GameBatch", "Examples"):
         from . import engine
         return getattr(engine, name)
     if name in ("MCTS", "MCTSArgs", "GuidedMCTS"):
         from . import mcts
         return getattr(mcts, name)
+    if name == "play_episodes":
+        from . import selfplay
+        return selfplay.play_episodes
     if name == "BatchedGame":
         from . import game
         return game.BatchedGame

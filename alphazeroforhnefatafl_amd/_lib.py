@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflGmctsStats, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRules,
+from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRules,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -49,6 +49,15 @@ SYMBOLS = [
     ("tafl_mcts_run_async_after", _i32, [_vp, _P(TaflMctsParams), _u64, _vp]),
     ("tafl_mcts_wait", _i32, [_vp]),
     ("tafl_selfplay_run", _i32, [_vp, _P(TaflMctsParams), _u32, _u64, _P(TaflPlay)]),
+    ("tafl_selfplay_record", _i32, [_vp, _P(TaflMctsParams), _P(TaflSelfplayOpts), _u32, _u64, _vp, _P(TaflPlay)]),
+    ("tafl_examples_create", _i32, [_vp, _u32, _u32, _u32, _P(_vp)]),
+    ("tafl_examples_destroy", _i32, [_vp]),
+    ("tafl_examples_clear", _i32, [_vp]),
+    ("tafl_examples_counts", _i32, [_vp, _P(_u32), _P(_u64)]),
+    ("tafl_examples_get_stats", _i32, [_vp, _P(TaflExamplesStats)]),
+    ("tafl_examples_finalize", _i32, [_vp, _vp]),
+    ("tafl_examples_read", _i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    ("tafl_examples_gather", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _i32]),
     ("tafl_mcts_get_stats", _i32, [_vp, _P(TaflMctsStats)]),
     ("tafl_mcts_root_children", _i32, [_vp, _P(TaflRootChild), _u32, _P(_u32)]),
     ("tafl_mcts_root_visits", _i32, [_vp, _P(_u32)]),

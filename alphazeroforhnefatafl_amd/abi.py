@@ -152,13 +152,24 @@ class TaflGmctsStats(C.Structure):
                 ("select_depth_sum", C.c_uint64), ("waiting", C.c_uint64), ("_reserved", C.c_uint64 * 2)]
 
 
+class TaflSelfplayOpts(C.Structure):
+    """tafl_selfplay_opts: how a recording self-play run (tafl_selfplay_record) chooses its plays."""
+    _fields_ = [("sample_seed", C.c_uint64), ("temp_moves", C.c_uint32), ("move_base", C.c_uint32), ("flags", C.c_uint32),
+                ("_reserved", C.c_uint32 * 3)]
+
+
+class TaflExamplesStats(C.Structure):
+    _fields_ = [("dropped", C.c_uint64), ("overflowed", C.c_uint64), ("bad_index", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
-                  "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64}
+                  "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
-                    ("tafl_mcts_stats", TaflMctsStats), ("tafl_gmcts_stats", TaflGmctsStats)]:
+                    ("tafl_mcts_stats", TaflMctsStats), ("tafl_gmcts_stats", TaflGmctsStats),
+                    ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

@@ -285,10 +285,11 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_init(Consts<NL> C, const Qu
 // served by ready slots, then issue the next slots (tafl_ops.hpp mcts_tree_step)
 // SP: a self-play run (tafl_selfplay_run): a game whose search is done plays its most visited root play on the batch state (soa, layout
 // <NLS, WS>) and starts its next search in the same launch; its plan counts from the launch in which that search began
-template <int NLS, int WS, int NL, int W, int PRESET, bool SP>
+// REC: a recording run (tafl_selfplay_record): the advance also draws the play and appends the move's training example (Ops::selfplay_advance_rec)
+template <int NLS, int WS, int NL, int W, int PRESET, bool SP, bool REC = false>
 __device__ __forceinline__ void mcts_tree_launch(const Consts<NL>& Carg, const MctsMem& M, double c_puct, uint32_t n_sims, uint32_t round, uint32_t planned, uint32_t probe_every,
                                                  uint32_t target, unsigned long long* stats, const unsigned long long* ctrl, uint32_t* work, uint32_t* work_count,
-                                                 uint32_t g_begin, uint32_t g_end, Quad* soa, const SelfPlay& sp) {
+                                                 uint32_t g_begin, uint32_t g_end, Quad* soa, const SelfPlay& sp, const SelfPlayRec* rec = nullptr) {
     const uint32_t g = g_begin + blockIdx.x * TAFL_BLOCK + threadIdx.x;     // this launch serves games g_begin .. g_end - 1
     // the tree phase of one half of the batch runs beside the other half's playouts (2 - 4 waves per SIMD): it is one latency-bound wave
     // per SIMD on the critical path of its half, so its instructions go first
@@ -301,7 +302,8 @@ __device__ __forceinline__ void mcts_tree_launch(const Consts<NL>& Carg, const M
         const bool adv = g < g_end && !live && sp.moves_done[g] < sp.n_moves;
         if (__ballot(live || adv) == 0ull) return;
         int r = 0;
-        if (adv) r = Ops<NL, W>::template selfplay_advance<NLS, WS>(M, g, soa, sp, n_sims, round, C);
+        if constexpr (REC) { if (adv) r = Ops<NL, W>::template selfplay_advance_rec<NLS, WS>(M, g, soa, sp, *rec, n_sims, round, C); }
+        else if (adv) r = Ops<NL, W>::template selfplay_advance<NLS, WS>(M, g, soa, sp, n_sims, round, C);
         live = live || r == 1;                                // the new search takes its first step in this launch
         const unsigned long long fin = __ballot(r == 2);      // games that made their last play
         if ((threadIdx.x & 63u) == 0 && fin) atomicAdd(&stats[ST_DONE], (unsigned long long)__popcll(fin));
@@ -373,6 +375,76 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_tree_selfplay(Consts<NL> Ca
                                                                    uint32_t target, unsigned long long* stats, const unsigned long long* ctrl, uint32_t* work, uint32_t* work_count,
                                                                    uint32_t g_begin, uint32_t g_end, Quad* soa, SelfPlay sp) {
     mcts_tree_launch<NLS, WS, NL, W, PRESET, true>(Carg, M, c_puct, n_sims, round, planned, probe_every, target, stats, ctrl, work, work_count, g_begin, g_end, soa, sp);
+}
+
+// the recording run's tree phase (tafl_selfplay_record): an instantiation of its own, so that k_mcts_tree_selfplay stays what it was
+template <int NLS, int WS, int NL, int W, int PRESET>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_mcts_tree_selfplay_rec(Consts<NL> Carg, MctsMem M, double c_puct, uint32_t n_sims, uint32_t round, uint32_t planned, uint32_t probe_every,
+                                                                       uint32_t target, unsigned long long* stats, const unsigned long long* ctrl, uint32_t* work, uint32_t* work_count,
+                                                                       uint32_t g_begin, uint32_t g_end, Quad* soa, SelfPlay sp, SelfPlayRec rec) {
+    mcts_tree_launch<NLS, WS, NL, W, PRESET, true, true>(Carg, M, c_puct, n_sims, round, planned, probe_every, target, stats, ctrl, work, work_count, g_begin, g_end, soa, sp, &rec);
+}
+
+// z and the final mark of every recorded example, from the CURRENT status of its game in the batch (tafl_examples_finalize): one lane per game
+template <int NL>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_examples_finalize(const Quad* soa, ExamplesMem X) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= X.G) return;
+    const uint32_t flags = soa[(size_t)((2 * NL + 4) / 4) * X.G + g].w;
+    const uint32_t len = X.len[g] < X.max_moves ? X.len[g] : X.max_moves;
+    for (uint32_t j = 0; j < len; ++j) {
+        const size_t e = (size_t)j * X.G + g;
+        uint8_t fin; const float z = example_outcome(flags, (X.info[e] >> 16) & 0xFFu, fin);
+        X.z[e] = z; X.fin[e] = fin;
+    }
+}
+
+// Minibatch rows (tafl_examples_gather): row i = example index[i] under symmetry sym[i].  The dense policy row (4 * action_size bytes, at
+// most K words non-zero) is built in LDS and streamed out with full-width stores: the row in LDS is all zero between two examples (every
+// thread clears the words it has just read), so an example costs the scatter of its <= K entries, two barriers and the stream.  One
+// workgroup serves examples blockIdx.x, blockIdx.x + gridDim.x, ...  VEC: `pi` is 16-byte aligned (action_size is a multiple of 4).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_examples_gather(ExamplesMem X, const uint32_t* index, const uint8_t* sym, uint32_t count, uint32_t n, uint32_t A,
+                                                         uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* fin) {
+    extern __shared__ __align__(16) float lds_row[];                          // [A]
+    for (uint32_t v = threadIdx.x; v < A; v += 256) lds_row[v] = 0.0f;
+    __syncthreads();
+    const uint32_t nn = n * n;
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        const uint32_t e = index[i], g = e % X.G, j = e / X.G;
+        const bool ok = j < X.max_moves && j < X.len[g];          // (block-uniform)
+        const uint32_t s = sym ? (sym[i] & 7u) : 0u;
+        const uint32_t info = ok ? X.info[e] : 0u, nc = info & 0xFFFFu;
+        if (pi && threadIdx.x < nc) {
+            const double N = (double)(X.played[e] >> 16);          // sum of the Nsa, noted when the example was recorded
+            for (uint32_t k = threadIdx.x; k < nc; k += 256) {
+                const uint32_t w = X.pol[((size_t)j * X.K + k) * X.G + g], a = w & 0xFFFFu;
+                lds_row[s ? sym_action(s, a, n) : a] = (float)((double)(w >> 16) / N);
+            }
+        }
+        if (boards && threadIdx.x < nn) {
+            const uint32_t t = threadIdx.x;
+            const uint32_t w = ok ? X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] : 0u;
+            boards[(size_t)i * nn + (s ? sym_tile(s, t, n) : t)] = (uint8_t)(w >> (8u * (t & 3u)));
+        }
+        if (threadIdx.x == 0) {
+            if (!ok) atomicAdd(&X.counters[EX_BAD_INDEX], 1ull);
+            if (sides) sides[i] = (uint8_t)((info >> 16) & 0xFFu);
+            if (z) z[i] = ok ? X.z[e] : 0.0f;
+            if (fin) fin[i] = ok ? X.fin[e] : (uint8_t)0;
+        }
+        if (pi) {
+            __syncthreads();
+            if constexpr (VEC) {
+                float4* dst = reinterpret_cast<float4*>(pi + (size_t)i * A); float4* src = reinterpret_cast<float4*>(lds_row);
+                for (uint32_t v = threadIdx.x; v < A / 4u; v += 256) { dst[v] = src[v]; src[v] = make_float4(0.f, 0.f, 0.f, 0.f); }
+            } else {
+                float* dst = pi + (size_t)i * A;
+                for (uint32_t v = threadIdx.x; v < A; v += 256) { dst[v] = lds_row[v]; lds_row[v] = 0.0f; }
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // the dominant kernel: one seeded random playout per entry of the round's work list (slot, game), state resident in registers.
@@ -738,6 +810,7 @@ struct SearchPlan {
     uint32_t parts, slots, planned, probe_every, next_round, max_rounds;
     unsigned long long ctrl0[4];     // initial control words (CT_*): source of an asynchronous copy
     SelfPlay selfplay;               // n_moves != 0: a self-play run (tafl_selfplay_run)
+    bool recording; SelfPlayRec rec; // a recording run (tafl_selfplay_record): k_mcts_tree_selfplay_rec
     SearchPart P[TAFL_MCTS_MAX_PARTS];
 };
 
@@ -1286,7 +1359,10 @@ static int mcts_enqueue_rounds(tafl_batch* b, uint32_t count, bool stagger) {
             uint32_t* wc_now = pk.wc + (i & 1u) * TAFL_MCTS_MAX_SLOTS; uint32_t* wc_next = pk.wc + ((i + 1u) & 1u) * TAFL_MCTS_MAX_SLOTS;
             {
                 SpanGuard sg(c, KC_MCTS_TREE, pk.s);
-                if (sp.selfplay.n_moves)
+                if (sp.selfplay.n_moves && sp.recording)
+                    DISPATCH_ARENA_PRESET(c, hipLaunchKernelGGL((k_mcts_tree_selfplay_rec<NLS, WS, NL, W, PRESET>), dim3(pk.grid_tree), dim3(TAFL_BLOCK), TAFL_UNDO_LDS_BYTES(TAFL_MCTS_UNDO_CAP), pk.s, CC, M, p->c_puct, p->n_sims, i, sp.planned, sp.probe_every,
+                                                          sp.slots, st, ctrl, pk.wl, wc_now, pk.g0, pk.g1, b->soa, sp.selfplay, sp.rec));
+                else if (sp.selfplay.n_moves)
                     DISPATCH_ARENA_PRESET(c, hipLaunchKernelGGL((k_mcts_tree_selfplay<NLS, WS, NL, W, PRESET>), dim3(pk.grid_tree), dim3(TAFL_BLOCK), TAFL_UNDO_LDS_BYTES(TAFL_MCTS_UNDO_CAP), pk.s, CC, M, p->c_puct, p->n_sims, i, sp.planned, sp.probe_every,
                                                           sp.slots, st, ctrl, pk.wl, wc_now, pk.g0, pk.g1, b->soa, sp.selfplay));
                 else
@@ -1407,7 +1483,7 @@ static int mcts_keep_capacity(tafl_batch* b, uint32_t n_sims) {
     return TAFL_OK;
 }
 
-static int mcts_begin_enqueue(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves) {
+static int mcts_begin_enqueue(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves, const SelfPlayRec* rec) {
     if (!b || !p) return fail(TAFL_ERR_INVALID_ARG, "null argument");
     if (p->flags & ~(uint32_t)TAFL_MCTS_FLAGS_KNOWN) return fail(TAFL_ERR_UNSUPPORTED, "tafl_mcts_params.flags: unknown bits set");
     if (p->n_sims == 0) return fail(TAFL_ERR_INVALID_ARG, "n_sims must be > 0");
@@ -1423,6 +1499,7 @@ static int mcts_begin_enqueue(tafl_batch* b, const tafl_mcts_params* p, uint64_t
     HIPCHK(hipSetDevice(c->device));
     SearchPlan& sp = b->plan;
     sp.p = *p; sp.base = game_id_base; sp.next_round = 0; sp.fused = false;
+    sp.recording = n_moves && rec; if (sp.recording) sp.rec = *rec;
     sp.selfplay.n_moves = n_moves; sp.selfplay.moves_done = nullptr; sp.selfplay.start_round = nullptr; sp.selfplay.plays = nullptr;
     MctsMem& M = sp.M; M = b->mem;
     M.node_cap = keep ? b->mem.node_cap : p->n_sims + 1; M.edge_cap = b->mem.edge_cap; M.flags = p->flags & TAFL_MCTS_FLAG_FPU_INF;
@@ -1563,8 +1640,8 @@ static void search_streams_drain(tafl_batch* b) {
 // the control block copy, rounds on every partition's stream): the streams are drained before the error is reported, so that no launch
 // runs on while the caller frees, grows or rewrites what it reads.  (A failure BEFORE the join of an earlier search leaves that search
 // in flight and active: it is joined like any other.)
-static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves = 0) {
-    const int rc = mcts_begin_enqueue(b, p, game_id_base, after, n_moves);
+static int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, tafl_batch* after, uint32_t n_moves = 0, const SelfPlayRec* rec = nullptr) {
+    const int rc = mcts_begin_enqueue(b, p, game_id_base, after, n_moves, rec);
     if (rc != TAFL_OK && b && !b->plan.active) search_streams_drain(b);
     return rc;
 }
@@ -1615,6 +1692,213 @@ int tafl_selfplay_run(tafl_batch* b, const tafl_mcts_params* p, uint32_t n_moves
         tafl_ctx* c = b->ctx;
         HIPCHK(hipMemcpyAsync(out_plays, b->sp_plays.p, sizeof(tafl_play) * (size_t)b->n * n_moves, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return TAFL_OK;
+}
+
+// ---- training examples ----------------------------------------------------------------------------------------
+struct tafl_examples {
+    tafl_ctx* ctx;
+    uint32_t n_games, max_moves, max_children;
+    ExamplesMem mem;
+    DevBuf len, boards, info, played, move_no, pol, z, fin, counters;
+    DevBuf g_index, g_sym, g_boards, g_sides, g_pi, g_z, g_fin;      // staging of a gather with host pointers
+};
+#define EXCHK(ex, name) do { if (!(ex)) return fail(TAFL_ERR_INVALID_ARG, name ": null examples object"); HIPCHK(hipSetDevice((ex)->ctx->device)); } while (0)
+
+int tafl_examples_create(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint32_t max_children, tafl_examples** out) {
+    if (!c || !out || n_games == 0 || max_moves == 0 || max_children == 0 || max_children > 0xFFFFu)
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: bad argument (n_games, max_moves >= 1, max_children in 1..65535)");
+    if ((unsigned long long)n_games * max_moves > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: n_games * max_moves exceeds 32 bits");
+    HIPCHK(hipSetDevice(c->device));
+    tafl_examples* x = new (std::nothrow) tafl_examples();
+    if (!x) return fail(TAFL_ERR_OOM, "out of host memory");
+    c->live_batches += 1;                                    // (the context outlives its examples objects as it outlives its batches)
+    x->ctx = c; x->n_games = n_games; x->max_moves = max_moves; x->max_children = max_children;
+    const size_t E = (size_t)n_games * max_moves, BW = ((size_t)c->n * c->n + 3) / 4;
+    if (x->len.ensure(4 * (size_t)n_games) || x->boards.ensure(4 * E * BW) || x->info.ensure(4 * E) || x->played.ensure(4 * E) || x->move_no.ensure(4 * E) ||
+        x->pol.ensure(4 * E * max_children) || x->z.ensure(4 * E) || x->fin.ensure(E) || x->counters.ensure(8 * EX_COUNTERS)) {
+        tafl_examples_destroy(x);
+        return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_examples_create)");
+    }
+    ExamplesMem& M = x->mem;
+    M.len = (uint32_t*)x->len.p; M.boards = (uint32_t*)x->boards.p; M.info = (uint32_t*)x->info.p; M.played = (uint32_t*)x->played.p; M.move_no = (uint32_t*)x->move_no.p;
+    M.pol = (uint32_t*)x->pol.p; M.z = (float*)x->z.p; M.fin = (uint8_t*)x->fin.p; M.counters = (unsigned long long*)x->counters.p;
+    M.G = n_games; M.max_moves = max_moves; M.K = max_children; M.BW = (uint32_t)BW;
+    const int rc = tafl_examples_clear(x);
+    if (rc) { tafl_examples_destroy(x); return rc; }
+    *out = x;
+    return TAFL_OK;
+}
+int tafl_examples_destroy(tafl_examples* x) {
+    if (!x) return TAFL_OK;
+    (void)hipSetDevice(x->ctx->device);
+    (void)hipStreamSynchronize(x->ctx->stream);
+    for (DevBuf* d : { &x->len, &x->boards, &x->info, &x->played, &x->move_no, &x->pol, &x->z, &x->fin, &x->counters, &x->g_index, &x->g_sym, &x->g_boards, &x->g_sides, &x->g_pi, &x->g_z, &x->g_fin }) d->release();
+    x->ctx->live_batches -= 1;
+    delete x;
+    return TAFL_OK;
+}
+int tafl_examples_clear(tafl_examples* x) {
+    EXCHK(x, "tafl_examples_clear");
+    hipStream_t s = x->ctx->stream;
+    HIPCHK(hipMemsetAsync(x->len.p, 0, 4 * (size_t)x->n_games, s));
+    HIPCHK(hipMemsetAsync(x->counters.p, 0, 8 * EX_COUNTERS, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return TAFL_OK;
+}
+int tafl_examples_counts(tafl_examples* x, uint32_t* out_len, uint64_t* out_total) {
+    EXCHK(x, "tafl_examples_counts");
+    hipStream_t s = x->ctx->stream;
+    std::vector<uint32_t> h(x->n_games);
+    HIPCHK(hipMemcpyAsync(h.data(), x->len.p, 4 * (size_t)x->n_games, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    uint64_t tot = 0;
+    for (uint32_t g = 0; g < x->n_games; ++g) { tot += h[g]; if (out_len) out_len[g] = h[g]; }
+    if (out_total) *out_total = tot;
+    return TAFL_OK;
+}
+int tafl_examples_get_stats(tafl_examples* x, tafl_examples_stats* out) {
+    EXCHK(x, "tafl_examples_get_stats");
+    if (!out) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_get_stats: null argument");
+    hipStream_t s = x->ctx->stream;
+    unsigned long long h[EX_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, x->counters.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    memset(out, 0, sizeof *out);
+    out->dropped = h[EX_DROPPED]; out->overflowed = h[EX_OVERFLOWED]; out->bad_index = h[EX_BAD_INDEX];
+    out->device_bytes = x->len.cap + x->boards.cap + x->info.cap + x->played.cap + x->move_no.cap + x->pol.cap + x->z.cap + x->fin.cap + x->counters.cap +
+                        x->g_index.cap + x->g_sym.cap + x->g_boards.cap + x->g_sides.cap + x->g_pi.cap + x->g_z.cap + x->g_fin.cap;      // (the staging of host-pointer gathers included)
+    return TAFL_OK;
+}
+
+// tafl_selfplay_run with the play of the opening moves drawn from the visit counts and every move's training example left in `ex`
+int tafl_selfplay_record(tafl_batch* b, const tafl_mcts_params* p, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base, tafl_examples* ex, tafl_play* out_plays) {
+    if (!p || !o || n_moves == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: bad argument");
+    if (o->flags != 0 || o->_reserved[0] != 0 || o->_reserved[1] != 0 || o->_reserved[2] != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_opts: flags and reserved words must be 0");
+    if (p->flags & TAFL_MCTS_FLAG_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_record: TAFL_MCTS_FLAG_KEEP_TREE is not supported (no re-root inside a self-play run)");
+    if ((unsigned long long)n_moves * p->n_sims + p->sim_offset > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: sim_offset + n_moves * n_sims exceeds 32 bits");
+    if ((unsigned long long)o->move_base + n_moves > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: move_base + n_moves exceeds 32 bits");
+    if (p->n_sims > 0xFFFFu) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: n_sims must be below 65536 (Nsa is stored in 16 bits)");
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: null batch");
+    if (ex && (ex->n_games != b->n || ex->ctx->device != b->ctx->device || ex->ctx->n != b->ctx->n))
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: the examples object was created for another batch size, board or device");
+    SelfPlayRec rec{};
+    if (ex) rec.ex = ex->mem;
+    rec.sample_seed = o->sample_seed; rec.game_id_base = game_id_base; rec.temp_moves = o->temp_moves; rec.move_base = o->move_base;
+    if (ex) { HIPCHK(hipSetDevice(ex->ctx->device)); HIPCHK(hipStreamSynchronize(ex->ctx->stream)); }      // (clears and gathers of another context's stream)
+    int rc = mcts_begin(b, p, game_id_base, nullptr, n_moves, &rec);
+    if (rc == TAFL_OK) rc = tafl_mcts_wait(b);
+    b->ran = false;
+    b->tree_live = false; b->g_tree_live = false;
+    if (rc) return rc;
+    if (out_plays) {
+        tafl_ctx* c = b->ctx;
+        HIPCHK(hipMemcpyAsync(out_plays, b->sp_plays.p, sizeof(tafl_play) * (size_t)b->n * n_moves, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    return TAFL_OK;
+}
+
+int tafl_examples_finalize(tafl_examples* x, tafl_batch* b) {
+    EXCHK(x, "tafl_examples_finalize");
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_finalize: null batch");
+    if (b->n != x->n_games || b->ctx->device != x->ctx->device) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_finalize: the batch has another size or device");
+    if (b->plan.active) { const int rc = tafl_mcts_wait(b); if (rc) return rc; }
+    tafl_ctx* c = b->ctx;
+    if (c != x->ctx) HIPCHK(hipStreamSynchronize(x->ctx->stream));
+    DISPATCH_NLW(c, hipLaunchKernelGGL((k_examples_finalize<NL>), dim3(grid_of(b->n)), dim3(TAFL_BLOCK), 0, c->stream, b->soa, x->mem));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return TAFL_OK;
+}
+
+// the sparse form of examples, for hosts that store or inspect them: host pointers, any output may be NULL
+int tafl_examples_read(tafl_examples* x, const uint32_t* index, uint32_t count, uint32_t* n_children, uint8_t* overflow, uint32_t* played, uint32_t* move_no,
+                       uint32_t* actions, uint32_t* visits) {
+    EXCHK(x, "tafl_examples_read");
+    if (!index && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read: null index");
+    hipStream_t s = x->ctx->stream;
+    const size_t K = x->max_children, G = x->n_games;
+    // the arrays are example-major in j: only the prefix up to the highest j asked for is copied
+    size_t jmax = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const size_t j = index[i] / G;
+        if (j >= x->max_moves) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        if (j > jmax) jmax = j;
+    }
+    const size_t E = count ? (jmax + 1) * G : 0;
+    std::vector<uint32_t> len(G), info(E), pl(E), mv(E), pol((actions || visits) ? E * K : 0);
+    if (count == 0) return TAFL_OK;
+    HIPCHK(hipMemcpyAsync(len.data(), x->len.p, 4 * G, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(info.data(), x->info.p, 4 * E, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(pl.data(), x->played.p, 4 * E, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(mv.data(), x->move_no.p, 4 * E, hipMemcpyDeviceToHost, s));
+    if (!pol.empty()) HIPCHK(hipMemcpyAsync(pol.data(), x->pol.p, 4 * E * K, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < count; ++i) {
+        const size_t e = index[i], g = e % G, j = e / G;
+        if (j >= x->max_moves || j >= len[g]) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        const uint32_t nc = info[e] & 0xFFFFu;
+        if (n_children) n_children[i] = nc;
+        if (overflow) overflow[i] = (info[e] & kExOverflow) ? 1 : 0;
+        if (played) played[i] = pl[e] & 0xFFFFu;
+        if (move_no) move_no[i] = mv[e];
+        for (size_t k = 0; k < K && !pol.empty(); ++k) {
+            const uint32_t w = k < nc ? pol[(j * K + k) * G + g] : 0u;
+            if (actions) actions[(size_t)i * K + k] = w & 0xFFFFu;
+            if (visits) visits[(size_t)i * K + k] = w >> 16;
+        }
+    }
+    return TAFL_OK;
+}
+
+static int examples_gather_launch(tafl_examples* x, const uint32_t* index, const uint8_t* sym, uint32_t count, uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* fin) {
+    tafl_ctx* c = x->ctx;
+    const uint32_t A = c->n * c->n * 2u * (c->n - 1u);
+    const uint32_t grid = count < 8192u ? count : 8192u;
+    if (((uintptr_t)pi & 15u) == 0)
+        hipLaunchKernelGGL((k_examples_gather<true>), dim3(grid), dim3(256), A * sizeof(float), c->stream, x->mem, index, sym, count, c->n, A, boards, sides, pi, z, fin);
+    else
+        hipLaunchKernelGGL((k_examples_gather<false>), dim3(grid), dim3(256), A * sizeof(float), c->stream, x->mem, index, sym, count, c->n, A, boards, sides, pi, z, fin);
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
+int tafl_examples_gather(tafl_examples* x, const uint32_t* index, const uint8_t* sym, uint32_t count, uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* final_, int ptrs_are_device) {
+    EXCHK(x, "tafl_examples_gather");
+    if (!index && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather: null index");
+    if (count == 0) return TAFL_OK;
+    tafl_ctx* c = x->ctx; hipStream_t s = c->stream;
+    if (ptrs_are_device) return examples_gather_launch(x, index, sym, count, boards, sides, pi, z, final_);       // (asynchronous on the context's stream, like the other device writers)
+    // host pointers: every index is checked first, then the rows are gathered into device staging and copied out, a chunk at a time
+    {
+        std::vector<uint32_t> len(x->n_games);
+        HIPCHK(hipMemcpyAsync(len.data(), x->len.p, 4 * (size_t)x->n_games, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t g = index[i] % x->n_games, j = index[i] / x->n_games;
+            if (j >= x->max_moves || j >= len[g]) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+            if (sym && sym[i] > 7) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather: sym must be in 0..7");
+        }
+    }
+    const size_t A = (size_t)c->n * c->n * 2u * (c->n - 1u), nn = (size_t)c->n * c->n;
+    const uint32_t chunk = count < 8192u ? count : 8192u;       // (staging for what is asked for: a one-row gather holds one row)
+    NEED(x->g_index, 4 * (size_t)chunk); NEED(x->g_sym, chunk); NEED(x->g_sides, chunk); NEED(x->g_z, 4 * (size_t)chunk); NEED(x->g_fin, chunk);
+    if (boards) NEED(x->g_boards, nn * chunk);
+    if (pi) NEED(x->g_pi, 4 * A * chunk);
+    for (uint32_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint32_t k = count - i0 < chunk ? count - i0 : chunk;
+        HIPCHK(hipMemcpyAsync(x->g_index.p, index + i0, 4 * (size_t)k, hipMemcpyHostToDevice, s));
+        if (sym) HIPCHK(hipMemcpyAsync(x->g_sym.p, sym + i0, k, hipMemcpyHostToDevice, s));
+        const int rc = examples_gather_launch(x, (const uint32_t*)x->g_index.p, sym ? (const uint8_t*)x->g_sym.p : nullptr, k, boards ? (uint8_t*)x->g_boards.p : nullptr,
+                                              sides ? (uint8_t*)x->g_sides.p : nullptr, pi ? (float*)x->g_pi.p : nullptr, z ? (float*)x->g_z.p : nullptr, final_ ? (uint8_t*)x->g_fin.p : nullptr);
+        if (rc) return rc;
+        if (boards) HIPCHK(hipMemcpyAsync(boards + (size_t)i0 * nn, x->g_boards.p, nn * k, hipMemcpyDeviceToHost, s));
+        if (sides) HIPCHK(hipMemcpyAsync(sides + i0, x->g_sides.p, k, hipMemcpyDeviceToHost, s));
+        if (pi) HIPCHK(hipMemcpyAsync(pi + (size_t)i0 * A, x->g_pi.p, 4 * A * k, hipMemcpyDeviceToHost, s));
+        if (z) HIPCHK(hipMemcpyAsync(z + i0, x->g_z.p, 4 * (size_t)k, hipMemcpyDeviceToHost, s));
+        if (final_) HIPCHK(hipMemcpyAsync(final_ + i0, x->g_fin.p, k, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
     }
     return TAFL_OK;
 }

@@ -1,0 +1,87 @@
+// tafl_examples.hpp — training examples recorded by a self-play run (tafl_selfplay_record): the device-resident
+// buffer, the choice of the play (argmax or a draw in proportion to the visit counts, in integers), the result of an example and the
+// eight symmetries of the square on tiles and dense actions.  __host__ __device__ like everything in tafl_ops.hpp: the kernels run these
+// functions one game (or one example) per lane, tests/hostsim runs the same code on the CPU.
+#pragma once
+#include "tafl_core.hpp"
+
+#define TAFL_DRAW_VALUE 1e-4     /* getGameEnded draw convention, DESIGN.md: the value of a drawn terminal in the search and z of a drawn game */
+
+namespace tafl {
+
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TAFL_COUNT_ADD(p, v) atomicAdd((p), (unsigned long long)(v))
+#else
+#define TAFL_COUNT_ADD(p, v) (*(p) += (v))
+#endif
+
+// Example (j, g) - the j-th example of game g - has index e = j * G + g in every per-example array (a wave's stores are contiguous).
+enum { EX_DROPPED = 0, EX_OVERFLOWED = 1, EX_BAD_INDEX = 2, EX_COUNTERS = 4 };
+constexpr uint32_t kExOverflow = 1u << 24;       // ExamplesMem::info: the root had more than K visited children, none is stored
+struct ExamplesMem {
+    uint32_t* len;               // [G] examples of game g
+    uint32_t* boards;            // [(j * BW + w) * G + g] board_to_matrix bytes of the position before the play, four tiles per word (tile t: byte t & 3 of word t >> 2)
+    uint32_t* info;              // [e] n_children | side to move (TAFL_ATTACKER / TAFL_DEFENDER) << 16 | kExOverflow
+    uint32_t* played;            // [e] dense action index of the play made | N = sum of the stored Nsa << 16
+    uint32_t* move_no;           // [e] number of the move in the episode (move_base + move inside the run)
+    uint32_t* pol;               // [(j * K + k) * G + g] k-th visited root child in canonical order: action | Nsa << 16
+    float* z;                    // [e] result seen from the example's side to move (tafl_examples_finalize)
+    uint8_t* fin;                // [e] 1: z is final
+    unsigned long long* counters;   // [EX_COUNTERS]
+    uint32_t G, max_moves, K, BW;
+};
+// what a recording run adds to SelfPlay: ex.len == nullptr records nothing (the plays are still drawn)
+struct SelfPlayRec {
+    ExamplesMem ex;
+    uint64_t sample_seed, game_id_base;
+    uint32_t temp_moves, move_base;
+};
+
+// ---- the eight symmetries of the square -----------------------------------------------------------------------------------------
+// bit 2 of sym transposes (r, c) -> (c, r) first, then bit 0 mirrors the rows r -> n-1-r, then bit 1 mirrors the columns c -> n-1-c.
+// Tiles are r * n + c.
+static TAFL_HD uint32_t sym_tile(uint32_t sym, uint32_t t, uint32_t n) {
+    uint32_t r = t / n, c = t % n;
+    if (sym & 4u) { const uint32_t x = r; r = c; c = x; }
+    if (sym & 1u) r = n - 1u - r;
+    if (sym & 2u) c = n - 1u - c;
+    return r * n + c;
+}
+// dense action (include/taflhip.h: (from tile) * 2(n-1) + slot, slots V+ V- H+ H- by distance) -> from tile and destination tile
+static TAFL_HD void action_tiles(uint32_t a, uint32_t n, uint32_t& from, uint32_t& to) {
+    const uint32_t nm = n - 1u, t = a / (2u * nm), s = a % (2u * nm), r = t / n, c = t % n;
+    from = t;
+    if (s < nm - r) to = (r + s + 1u) * n + c;
+    else if (s < nm) to = (r - (s - (nm - r) + 1u)) * n + c;
+    else if (s < nm + (nm - c)) to = r * n + c + (s - nm + 1u);
+    else to = r * n + c - (s - nm - (nm - c) + 1u);
+}
+static TAFL_HD uint32_t tiles_action(uint32_t from, uint32_t to, uint32_t n) {
+    const uint32_t nm = n - 1u, r = from / n, c = from % n, r2 = to / n, c2 = to % n;
+    uint32_t s;
+    if (c2 == c) s = r2 > r ? r2 - r - 1u : (nm - r) + (r - r2) - 1u;
+    else s = c2 > c ? nm + (c2 - c) - 1u : nm + (nm - c) + (c - c2) - 1u;
+    return from * 2u * nm + s;
+}
+// an action under a symmetry: its from and to tiles transformed and encoded again
+static TAFL_HD uint32_t sym_action(uint32_t sym, uint32_t a, uint32_t n) {
+    uint32_t from, to; action_tiles(a, n, from, to);
+    return tiles_action(sym_tile(sym, from, n), sym_tile(sym, to, n), n);
+}
+
+// z of an example whose side to move was `side` (TAFL_ATTACKER / TAFL_DEFENDER), from the game's current flags word: +1 that side won,
+// -1 it lost, TAFL_DRAW_VALUE (1e-4) a draw; fin = 0 and z = 0 while the game is going on
+static TAFL_HD float example_outcome(uint32_t flags, uint32_t side, uint8_t& fin) {
+    const uint32_t status = TAFL_F_STATUS(flags);
+    fin = status != TAFL_STATUS_ONGOING ? 1 : 0;
+    if (status == TAFL_STATUS_WIN) return ((TAFL_F_WINNER(flags) != 0u) == (side != 0u)) ? 1.0f : -1.0f;
+    return status == TAFL_STATUS_DRAW ? (float)TAFL_DRAW_VALUE : 0.0f;
+}
+
+// the word (sample_seed, global game id, move number in the episode) draws the play of a move with: independent of the sharding
+static TAFL_HD uint32_t selfplay_rand(uint64_t sample_seed, uint64_t game_id, uint32_t move_no) {
+    using E = Engine<2, 7>;
+    return E::ply_rand(E::sim_key(E::game_key(sample_seed, game_id), move_no), 0u);
+}
+
+}  // namespace tafl

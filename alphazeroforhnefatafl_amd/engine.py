@@ -13,7 +13,8 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflGmctsStats, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflState)
+from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
+                  TaflSelfplayOpts, TaflState)
 
 KC_MOVEGEN, KC_STEP, KC_ROLLOUT, KC_MCTS_TREE, KC_MCTS_ROLLOUT = range(5)
 
@@ -65,6 +66,11 @@ class BatchedGameLogic:
         if fen is not None:
             b.reset_fen(fen, self.rules.starting_side if side_to_play is None else side_to_play)
         return b
+
+    def new_examples(self, n_games: int, max_moves: int, max_children: int) -> "Examples":
+        """A device-resident buffer of training examples for batches of `n_games` games: room for `max_moves` examples per game with up
+        to `max_children` policy entries each (max_children >= n_sims can never overflow).  Filled by GameBatch.selfplay_record."""
+        return Examples(self, n_games, max_moves, max_children)
 
     def state_from_fen(self, fen: str, side_to_play: int | None = None) -> TaflState:
         st = TaflState()
@@ -201,6 +207,18 @@ class GameBatch:
         p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags)
         plays = (TaflPlay * (self.n * n_moves))() if want_plays else None
         check(lib().tafl_selfplay_run(self._h, C.byref(p), n_moves, game_id_base, plays))
+        return plays
+
+    def selfplay_record(self, examples: "Examples | None", n_moves: int, n_sims: int, c_puct: float, seed: int, max_rollout_plies: int,
+                        game_id_base: int = 0, sim_offset: int = 0, flags: int = 0, sample_seed: int = 0, temp_moves: int = 0,
+                        move_base: int = 0, want_plays: bool = True):
+        """selfplay_run that leaves one training example per game and move in `examples` (tafl_selfplay_record): the play of move
+        M = move_base + m is drawn in proportion to the visit counts while M < temp_moves (keyed by sample_seed, the global game id and M),
+        the most visited one afterwards, so temp_moves = 0 plays exactly what selfplay_run plays.  `examples` None: only the plays."""
+        p = TaflMctsParams(n_sims, max_rollout_plies, c_puct, seed, sim_offset, flags)
+        o = TaflSelfplayOpts(sample_seed, temp_moves, move_base, 0)
+        plays = (TaflPlay * (self.n * n_moves))() if want_plays else None
+        check(lib().tafl_selfplay_record(self._h, C.byref(p), C.byref(o), n_moves, game_id_base, examples._h if examples is not None else None, plays))
         return plays
 
     def mcts_wait(self):
@@ -360,3 +378,103 @@ class GameBatch:
         out = (C.c_uint32 * self.n)()
         check(lib().tafl_gmcts_tree_nodes(self._h, out))
         return out
+
+
+class Examples:
+    """Training examples (board, side to move, sparse search policy, play, result z) in HBM (tafl_examples).  Example j of game g has the
+    index j * n_games + g.  The object outlives runs and batches: an episode may be recorded in several runs, a trainer may keep several."""
+
+    def __init__(self, logic: BatchedGameLogic, n_games: int, max_moves: int, max_children: int):
+        self.logic = logic
+        self.n_games, self.max_moves, self.max_children = n_games, max_moves, max_children
+        self._h = C.c_void_p()
+        check(lib().tafl_examples_create(logic._h, n_games, max_moves, max_children, C.byref(self._h)))
+        logic._batches.add(self)          # closed with the context, like its batches
+
+    def close(self):
+        if self._h:
+            lib().tafl_examples_destroy(self._h)
+            self._h = C.c_void_p()
+            self.logic._batches.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def clear(self):
+        """Every game back to 0 examples, the counters back to 0."""
+        check(lib().tafl_examples_clear(self._h))
+
+    def counts(self):
+        """(examples per game [n_games], their sum)."""
+        out, tot = (C.c_uint32 * self.n_games)(), C.c_uint64()
+        check(lib().tafl_examples_counts(self._h, out, C.byref(tot)))
+        return out, tot.value
+
+    def stats(self) -> TaflExamplesStats:
+        """dropped (a game already held max_moves), overflowed (more than max_children visited root children), bad_index, device_bytes."""
+        st = TaflExamplesStats()
+        check(lib().tafl_examples_get_stats(self._h, C.byref(st)))
+        return st
+
+    def finalize(self, batch: GameBatch):
+        """z and the final mark of every example from the CURRENT status of its game in `batch`: +1 / -1 / 1e-4 seen from the example's
+        side to move; examples of games still going on keep z = 0, final = 0 (call it again after the next run)."""
+        check(lib().tafl_examples_finalize(self._h, batch._h))
+
+    def read(self, index):
+        """The sparse form of the examples `index` as numpy arrays: (n_children [k], overflow [k], played [k], move_no [k],
+        actions [k, max_children], visits [k, max_children]) - the visited root children in canonical order (tafl_examples_read)."""
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        k, K = int(idx.size), self.max_children
+        nc, ov, pl, mv = np.zeros(k, np.uint32), np.zeros(k, np.uint8), np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        acts, vis = np.zeros((k, K), np.uint32), np.zeros((k, K), np.uint32)
+        vp = C.c_void_p
+        check(lib().tafl_examples_read(self._h, idx.ctypes.data_as(vp), k, nc.ctypes.data_as(vp), ov.ctypes.data_as(vp), pl.ctypes.data_as(vp),
+                                       mv.ctypes.data_as(vp), acts.ctypes.data_as(vp), vis.ctypes.data_as(vp)))
+        return nc, ov, pl, mv, acts, vis
+
+    def gather(self, index, sym=None, device: bool = False):
+        """Minibatch rows (boards uint8 [k, n, n], sides uint8 [k], pi float32 [k, action_size], z float32 [k], final uint8 [k]) of the
+        examples `index` under the board symmetries `sym` (0..7 each, None: identity).  device=False: `index` / `sym` are sequences or
+        numpy arrays and numpy arrays come back.  device=True: they are torch tensors (int32 / uint8) on the context's device, torch
+        tensors on that device come back and nothing crosses PCIe."""
+        n, A = self.logic.side_len, self.logic.action_size
+        if device:
+            import torch
+            dev = index.device
+            k = int(index.numel())
+            idx = index.contiguous()
+            if idx.dtype != torch.int32 or not idx.is_cuda or idx.device.index != self.logic.device:
+                raise ValueError("gather(device=True): index must be an int32 tensor on the context's device")
+            sy = None
+            if sym is not None:
+                sy = sym.contiguous()
+                if sy.dtype != torch.uint8 or sy.device != dev or sy.numel() != k:
+                    raise ValueError("gather(device=True): sym must be a uint8 tensor on the same device, one per index")
+            boards = torch.empty((k, n, n), dtype=torch.uint8, device=dev)
+            sides = torch.empty((k,), dtype=torch.uint8, device=dev)
+            pi = torch.empty((k, A), dtype=torch.float32, device=dev)
+            z = torch.empty((k,), dtype=torch.float32, device=dev)
+            fin = torch.empty((k,), dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the library writes on its own stream
+            check(lib().tafl_examples_gather(self._h, C.c_void_p(idx.data_ptr()), C.c_void_p(sy.data_ptr()) if sy is not None else None, k,
+                                             C.c_void_p(boards.data_ptr()), C.c_void_p(sides.data_ptr()), C.c_void_p(pi.data_ptr()),
+                                             C.c_void_p(z.data_ptr()), C.c_void_p(fin.data_ptr()), 1))
+            self.logic.sync()
+            return boards, sides, pi, z, fin
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        k = int(idx.size)
+        sy = None if sym is None else np.ascontiguousarray(sym, dtype=np.uint8)
+        if sy is not None and sy.size != k:
+            raise ValueError("gather: one sym per index")
+        boards, sides = np.zeros((k, n, n), np.uint8), np.zeros((k,), np.uint8)
+        pi, z, fin = np.zeros((k, A), np.float32), np.zeros((k,), np.float32), np.zeros((k,), np.uint8)
+        check(lib().tafl_examples_gather(self._h, idx.ctypes.data_as(C.c_void_p), sy.ctypes.data_as(C.c_void_p) if sy is not None else None, k,
+                                         boards.ctypes.data_as(C.c_void_p), sides.ctypes.data_as(C.c_void_p), pi.ctypes.data_as(C.c_void_p),
+                                         z.ctypes.data_as(C.c_void_p), fin.ctypes.data_as(C.c_void_p), 0))
+        return boards, sides, pi, z, fin

@@ -1,0 +1,36 @@
+"""Self-play episodes that leave their training examples on the device (include/taflhip.h tafl_selfplay_record):
+the executeEpisode loop of alpha-zero-general - the code base the reference's src/mcts.py belongs to - for a whole batch of games."""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .abi import TaflState
+from .engine import Examples, GameBatch
+from .mcts import MCTSArgs
+
+
+def _games_over(batch: GameBatch) -> int:
+    """Games of the batch that are over (one download, the status bytes counted as an array)."""
+    st = np.frombuffer(batch.download(), dtype=np.uint8).reshape(batch.n, C.sizeof(TaflState))
+    return int(np.count_nonzero(st[:, TaflState.status.offset]))
+
+
+def play_episodes(batch: GameBatch, examples: Examples, args: MCTSArgs, max_moves: int, moves_per_run: int = 8, *, sample_seed: int = 1,
+                  temp_moves: int = 0, flags: int = 0):
+    """Plays every game of `batch` from its current position until it is over or has made `max_moves` moves, `moves_per_run` moves per
+    device run (move_base continues the numbering, so the pieces equal one long run), recording one example per game and move in
+    `examples`; then writes the results z (Examples.finalize).  The first `temp_moves` moves of an episode are drawn in proportion to
+    the visit counts, the rest are the most visited plays.  Returns (examples per game, their sum, games that are over)."""
+    done, over = 0, _games_over(batch)
+    while done < max_moves and over < batch.n:
+        k = min(moves_per_run, max_moves - done)
+        batch.selfplay_record(examples, k, args.numMCTSSims, args.cpuct, args.seed, args.max_rollout_plies, game_id_base=args.game_id_base,
+                              sim_offset=done * args.numMCTSSims, flags=flags, sample_seed=sample_seed, temp_moves=temp_moves,
+                              move_base=done, want_plays=False)
+        done += k
+        over = _games_over(batch)
+    examples.finalize(batch)
+    lens, total = examples.counts()
+    return lens, total, over

@@ -400,6 +400,82 @@ int tafl_mcts_policy_device(tafl_batch* b, double temp, double* out, int out_is_
  * device math library's float64 pow (exact for temp == 1; within 4 ulp of the host's pow otherwise, tests/test_gpu_parity.py). */
 int tafl_mcts_policy_device_ex(tafl_batch* b, double temp, uint64_t tie_seed, uint64_t game_id_base, double* out, int out_is_device);
 
+/* ---- self-play that records training examples ---------------------------------------------------------------
+ * What an AlphaZero loop takes from self-play: per move one example (board, side to move, search policy pi, result z) - executeEpisode of
+ * alpha-zero-general, the code base src/mcts.py belongs to (the reference has no Coach) - left in HBM, and minibatches served from there.
+ * It replaces the synchronous loop { tafl_mcts_run; tafl_mcts_policy_device + tafl_encode_boards; choose on the host; tafl_step }.
+ *
+ * tafl_selfplay_record is tafl_selfplay_run (same searches: sim_offset + m * n_sims, same seed, same ply cap, no barrier between the moves)
+ * with two additions per game and move.  m = the move's number inside the run, M = opts->move_base + m its number in the episode,
+ * gid = game_id_base + game, visited root edges in canonical (= ascending action) order, N = sum of their Nsa:
+ *   the play   M >= temp_moves: the most visited child, first maximum - so temp_moves == 0 gives the plays and final states of
+ *              tafl_selfplay_run bit for bit.  M < temp_moves: drawn in proportion to the visit counts (pi at temp = 1, src/mcts.py:50-52)
+ *              in integers: r = ply_rand(sim_key(game_key(sample_seed, gid), M), 0) - the RNG words of the playouts -,
+ *              k = (r * N) >> 32, and the play is the first child whose running sum of Nsa exceeds k.  No floating point, no dependence on
+ *              the sharding.  A game that is over, or whose root has no visited child, plays nothing (all-zero play) and records nothing.
+ *   the example, appended to `ex` (NULL: nothing is recorded, the plays are still drawn) when the game makes the move:
+ *              the board_to_matrix bytes of the position BEFORE the play (what tafl_encode_boards writes), the side to move, the sparse
+ *              policy (n_children and per visited root child (action, Nsa); dense pi is never stored), the dense action index of the
+ *              play, and move_no = M.
+ * Example j of game g has the index j * n_games + g; a game appends at len[g].  Capacity, decided by bookkeeping:
+ *   ex->n_games != tafl_batch_size(b) (or another board size / device): TAFL_ERR_INVALID_ARG.
+ *   len[g] == max_moves: the game keeps playing and records no more; counted in tafl_examples_stats.dropped.
+ *   a root with more than max_children visited children: the example is written with n_children = 0 (its gather row is all zero), counted
+ *   in tafl_examples_stats.overflowed, and the game goes on.  A search of S simulations visits fewer than S root children, so
+ *   max_children >= n_sims can never overflow.  Neither is a fault of the search: tafl_mcts_stats.faults does not count them.
+ * n_sims must be below 65536.  TAFL_MCTS_FLAG_KEEP_TREE and the fused pipeline are rejected as tafl_selfplay_run rejects them
+ * (TAFL_ERR_UNSUPPORTED); opts->flags and the reserved words must be 0 (TAFL_ERR_UNSUPPORTED).  tafl_mcts_get_stats covers all searches.
+ *
+ * tafl_examples_create: room for max_moves examples per game of n_games games, max_children (1..65535) policy entries each:
+ *   n_games * max_moves * (4 * ceil(side_len^2 / 4) + 4 * max_children + 17) bytes on the context's device.  The object outlives runs and
+ *   batches (an episode may be played in several runs, move_base continuing the numbering); destroy it before its context.
+ * tafl_examples_clear: every game back to 0 examples, the counters back to 0.
+ * tafl_examples_counts: out_len[n_games] (may be NULL) and their sum (may be NULL).  tafl_examples_get_stats: the counters.
+ * tafl_examples_finalize: one kernel that reads each game's CURRENT status from `b` (same size and device as `ex`; a search in flight on
+ *   it is joined) and writes for every recorded example of that game z as float32 seen from the example's side to move: +1 that side
+ *   won, -1 it lost, 1e-4 a draw (the value the search gives a drawn terminal), final = 1; examples of a game that is still going on get
+ *   z = 0, final = 0, so the call can be repeated after the next run.
+ * tafl_examples_gather: minibatch rows.  For i < count, example index[i] under board symmetry sym[i] in 0..7 (sym == NULL: identity):
+ *   boards[i * side_len^2 ..]  the board bytes, transformed;  sides[i], z[i], final_[i] copied;
+ *   pi[i * tafl_action_size ..]  float32, zero except pi[sigma(action)] = (float)((double)Nsa / (double)N): the temp = 1 probs of
+ *   src/mcts.py:50-52 rounded once to float32.  Any output pointer may be NULL.
+ *   Symmetries (the eight of the square; every ruleset of this library is invariant under them): bit 2 of sym transposes (r, c) -> (c, r)
+ *   first, then bit 0 mirrors the rows r -> n-1-r, then bit 1 mirrors the columns c -> n-1-c.  A board byte moves to the transformed tile;
+ *   an action is transformed by transforming its from and to tiles and encoding them again (tafl_action_size above).
+ *   ptrs_are_device = 0: all pointers are host pointers; an index that names no recorded example (or a sym above 7) fails the call with
+ *   TAFL_ERR_INVALID_ARG before anything is written.  ptrs_are_device = 1: all pointers (index and sym included) are device pointers of
+ *   the context's device, the kernel is enqueued on the context's stream (tafl_sync joins it) and nothing crosses PCIe; such an index
+ *   gives an all-zero row and is counted in tafl_examples_stats.bad_index; sym is taken modulo 8. */
+typedef struct tafl_examples tafl_examples;      /* opaque, owned by the ctx's device */
+typedef struct tafl_selfplay_opts {
+    uint64_t sample_seed;
+    uint32_t temp_moves, move_base;
+    uint32_t flags;                              /* 0 */
+    uint32_t _reserved[3];
+} tafl_selfplay_opts;                            /* 32 bytes */
+typedef struct tafl_examples_stats {
+    uint64_t dropped;        /* examples not recorded because their game already held max_moves */
+    uint64_t overflowed;     /* examples recorded without a policy: more than max_children visited root children */
+    uint64_t bad_index;      /* rows of device-pointer gathers whose index named no recorded example */
+    uint64_t device_bytes;   /* device memory the object holds */
+} tafl_examples_stats;                           /* 32 bytes */
+int tafl_examples_create(tafl_ctx* ctx, uint32_t n_games, uint32_t max_moves, uint32_t max_children, tafl_examples** out);
+int tafl_examples_destroy(tafl_examples* ex);
+int tafl_examples_clear(tafl_examples* ex);
+int tafl_examples_counts(tafl_examples* ex, uint32_t* out_len, uint64_t* out_total);
+int tafl_examples_get_stats(tafl_examples* ex, tafl_examples_stats* out);
+int tafl_selfplay_record(tafl_batch* b, const tafl_mcts_params* params, const tafl_selfplay_opts* opts, uint32_t n_moves,
+                         uint64_t game_id_base, tafl_examples* ex, tafl_play* out_plays);
+int tafl_examples_finalize(tafl_examples* ex, tafl_batch* b);
+/* the sparse form of the examples index[0 .. count) (host pointers; an index that names no recorded example: TAFL_ERR_INVALID_ARG), for
+ * hosts that store or inspect them: n_children[i], overflow[i] (1: more than max_children visited children, no policy stored), played[i]
+ * (dense action index), move_no[i], and actions / visits [i * max_children + k] = the k-th visited root child in canonical order (0
+ * beyond n_children).  Any output may be NULL.  It copies the arrays of the examples 0 .. max j asked for of every game to the host: not a hot path. */
+int tafl_examples_read(tafl_examples* ex, const uint32_t* index, uint32_t count, uint32_t* n_children, uint8_t* overflow, uint32_t* played,
+                       uint32_t* move_no, uint32_t* actions, uint32_t* visits);
+int tafl_examples_gather(tafl_examples* ex, const uint32_t* index, const uint8_t* sym, uint32_t count,
+                         uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* final_, int ptrs_are_device);
+
 /* ---- guided MCTS: src/mcts.py:55-136 with the CALLER's network as nnet.predict (mcts.py:85), SURVEY.md section 8f rank 3 ---
  * Lock-step over the batch: each tafl_gmcts_step (i) expands every waiting leaf with the priors / value the caller computed
  * for it (mask by the legal moves, renormalise with numpy's pairwise np.sum, all-masked workaround: mcts.py:86-98) and backs
