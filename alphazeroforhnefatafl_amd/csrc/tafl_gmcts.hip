@@ -1,0 +1,304 @@
+// tafl_gmcts.hip — guided MCTS: the search whose leaves an external evaluator scores (tafl_guided.hpp), kernels and tafl_gmcts_* entry points.
+#include "tafl_internal.hpp"
+
+enum { GS_SIMS = 0, GS_PREDICTS, GS_TERMINAL, GS_FAULTS, GS_DEPTH, GS_WAITING, GS_COUNT };
+
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_init(Consts<NL> C, const Quad* soa, GuidedMem M) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st);
+    Guided<NL, W>::init_game(M, g, st);
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_step(Consts<NL> C, GuidedMem M, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                           uint32_t n_sims, unsigned long long* stats) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::step(M, g, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, C, gs);
+    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
+    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
+    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
+    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
+    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
+    if (M.kind[g] == 1) atomicAdd(&stats[GS_WAITING], 1ull);
+}
+// network input of the waiting leaves: board_to_matrix planes (game/main.rs:55-83), side to move, waiting flag; one thread per tile
+template <int NL, int W>
+__global__ __launch_bounds__(256) void k_gmcts_leaves(Consts<NL> C, GuidedMem M, uint8_t* boards, uint8_t* sides, uint8_t* waiting) {
+    const uint32_t nn = C.n * C.n;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)M.G * nn) return;
+    const uint32_t g = (uint32_t)(i / nn), t = (uint32_t)(i % nn), r = t / C.n, c = t % C.n, bit = r * (uint32_t)W + c;
+    const bool wait = M.kind[g] == 1;
+    const uint32_t L = wait ? M.leaf[g] : 0u;
+    const uint32_t* rec = (const uint32_t*)(M.node_state + ((size_t)L * M.G + g) * StateIO<NL>::QUADS);   // att[NL], def[NL], rep[4], meta[4]
+    const uint32_t aw = rec[bit >> 5], dw = rec[NL + (bit >> 5)], flags = rec[2 * NL + 7];
+    uint32_t v = 0;
+    if ((r == 0 || r == C.n - 1) && (c == 0 || c == C.n - 1)) v = 20;
+    if (r == C.n / 2 && c == C.n / 2) v = 30;
+    const bool d = (dw >> (bit & 31)) & 1u, a = (aw >> (bit & 31)) & 1u;
+    if (d) v += (r == TAFL_F_KROW(flags) && c == TAFL_F_KCOL(flags)) ? 5u : 1u; else if (a) v += 1u;
+    boards[i] = (uint8_t)v;
+    if (t == 0) { sides[g] = (uint8_t)((flags & TAFL_F_SIDE) ? TAFL_DEFENDER : TAFL_ATTACKER); waiting[g] = wait ? 1 : 0; }
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_root_children(Consts<NL> C, GuidedMem M, tafl_root_child* out, uint32_t max_children, uint32_t* out_n) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    out_n[g] = Guided<NL, W>::root_children(M, g, out + (size_t)g * max_children, max_children);
+}
+// dense root visit counts and the probs of src/mcts.py:43-53 (any temperature; temp == 0 as in k_mcts_policy)
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_root_dense(Consts<NL> C, GuidedMem M, uint32_t* visits, double* probs, uint32_t A, int one_hot, double inv_temp,
+                                                                 uint64_t tie_seed, uint64_t base) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    const GNode h = M.hdr[g];
+    if (!h.expanded) return;
+    const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+    // the legal edges are stored in ascending action order, zeros included: a zero count adds 0.0 to the sum (0 ** x == 0 for x > 0)
+    double sum = 0.0; uint32_t best = 0, ties = 0; bool any_n = false;
+    for (uint32_t j = 0; j < h.n_legal; ++j) {
+        const GEdge e = eb[j];
+        if (!one_hot && e.n != 0) sum += temp_weight(e.n, inv_temp);
+        if (e.n > best) { best = e.n; ties = 1; } else if (e.n == best && best > 0) ++ties;
+        any_n |= e.n != 0;
+    }
+    uint32_t pick = 0;
+    if (one_hot && tie_seed != 0 && ties > 1) pick = tie_pick(tie_seed, base + g, ties);
+    uint32_t seen = 0;
+    for (uint32_t j = 0; j < h.n_legal; ++j) {
+        const GEdge e = eb[j];
+        if (visits) visits[(size_t)g * A + e.action] = e.n;
+        if (probs && any_n) {
+            double p;
+            if (one_hot) { const bool is_max = e.n == best; p = (is_max && seen == pick) ? 1.0 : 0.0; seen += is_max ? 1u : 0u; }
+            else p = e.n != 0 ? temp_weight(e.n, inv_temp) / sum : 0.0;
+            probs[(size_t)g * A + e.action] = p;
+        }
+    }
+}
+
+// subtree reuse in guided mode: keep-init and advance (k_mcts_keep_init / k_mcts_advance on the guided arena)
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_keep_init(Consts<NL> C, const Quad* soa, GuidedMem M) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    if (M.node_top[g] == 0) { DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st); Guided<NL, W>::init_game(M, g, st); }
+    else Guided<NL, W>::keep_init(M, g);
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_advance(Consts<NL> C, GuidedMem M, Quad* soa, GEdge* dst, uint32_t* idmap, const uint32_t* actions, int live,
+                                                              uint32_t A, tafl_play* out_plays, tafl_effects* eff, uint32_t* bad) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    const GNode h = M.hdr[g];
+    const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+    uint32_t a = actions ? actions[g] : TAFL_ACTION_NONE, child = 0;
+    if (live && h.expanded) {
+        uint32_t best = 0;
+        for (uint32_t j = 0; j < h.n_legal; ++j) {                  // ascending action order: the first maximum
+            const GEdge e = eb[j];
+            if (actions ? e.action == a : e.n > best) { best = e.n; child = e.child; a = e.action; if (actions) break; }
+        }
+    }
+    DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st);
+    tafl_play p; tafl_effects e;
+    const bool played = advance_play<NL, W>(C, st, a, A, p, e);
+    if (played) StateIO<NL>::store_soa(soa, M.G, g, st);
+    const bool alone = !played && (a == TAFL_ACTION_NONE || e.code == TAFL_PLAY_GAME_OVER);
+    if (live && alone) Guided<NL, W>::keep_edges(M, dst, g);
+    else {
+        bool fresh = !(live && played && child != 0);
+        if (!fresh) {
+            Guided<NL, W>::reroot(M, dst, idmap, g, child);
+            if (!same_state<NL>(M.node_state + (size_t)g * StateIO<NL>::QUADS, st)) { atomicAdd(bad, 1u); fresh = true; }
+        }
+        if (fresh) Guided<NL, W>::init_game(M, g, st);
+    }
+    if (out_plays) out_plays[g] = p;
+    if (eff) eff[g] = e;
+}
+
+extern "C" {
+
+int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) { return tafl_gmcts_begin_ex(b, max_sims, edges_per_node, 0); }
+
+// TAFL_GMCTS_KEEP_TREE on a retained tree: the arena grows (contents kept) to the largest kept tree + max_sims + 1 nodes and + (max_sims + 1)
+// x edges_per_node edges, and only the per-search fields are reset
+static int gmcts_begin_keep(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) {
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
+    GuidedMem& M = b->gmem;
+    uint32_t mx[2];
+    int rc = arena_max(b, M.node_top, M.edge_top, mx);
+    if (rc) return rc;
+    const unsigned long long nodes = (unsigned long long)mx[0] + max_sims + 1, ecap = (unsigned long long)mx[1] + ((unsigned long long)max_sims + 1) * edges_per_node;
+    if (nodes > 0xFFFFFFFFull || ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_begin_ex: the retained tree and the new simulations exceed the arena's index range");
+    rc = arena_grow(b, {ArenaArray(b->g_node_state, sizeof(Quad) * q, M.node_state), ArenaArray(b->g_hdr, sizeof(GNode), M.hdr), ArenaArray(b->g_pedge, sizeof(uint32_t), M.pedge)},
+                    M.node_cap, nodes, ArenaArray(b->g_edges, sizeof(GEdge), M.edges), b->g_edges_alt, M.edge_cap, ecap);
+    if (rc != TAFL_OK) return rc;
+    HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_keep_init<t.NL, t.W>), c, n, t.CC, b->soa, M); });
+    HIPCHK(hipGetLastError());
+    b->g_max_sims = max_sims;
+    return TAFL_OK;
+}
+
+int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, uint32_t flags) {
+    if (!b || max_sims == 0 || edges_per_node == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_begin: bad argument");
+    if (flags & ~(uint32_t)TAFL_GMCTS_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: unknown flags");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
+    HIPCHK(hipSetDevice(c->device));
+    if (flags & TAFL_GMCTS_KEEP_TREE) { if (const int rc = join_search(b)) return rc; }
+    if ((flags & TAFL_GMCTS_KEEP_TREE) && b->g_has && b->g_tree_live) {
+        b->g_tree_live = false;
+        const int rc = gmcts_begin_keep(b, max_sims, edges_per_node);
+        if (rc == TAFL_OK) b->g_tree_live = true;
+        return rc;
+    }
+    b->g_tree_live = false;
+    const uint32_t node_cap = max_sims + 1;
+    const unsigned long long ecap = (unsigned long long)node_cap * edges_per_node;
+    if (ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_begin: edge arena too large");
+    NEED(b->g_node_state, sizeof(Quad) * q * node_cap * n); NEED(b->g_hdr, sizeof(GNode) * (size_t)node_cap * n);
+    NEED(b->g_pedge, sizeof(uint32_t) * (size_t)node_cap * n); NEED(b->g_edges, sizeof(GEdge) * (size_t)ecap * n);
+    NEED(b->g_node_top, 4 * (size_t)n); NEED(b->g_edge_top, 4 * (size_t)n); NEED(b->g_leaf, 4 * (size_t)n); NEED(b->g_kind, n); NEED(b->g_fault, n);
+    NEED(b->g_sims, 4 * (size_t)n); NEED(b->g_stats, sizeof(unsigned long long) * GS_COUNT);
+    GuidedMem& M = b->gmem;
+    b->g_node_state.bind(M.node_state); b->g_hdr.bind(M.hdr); b->g_pedge.bind(M.pedge); b->g_edges.bind(M.edges);
+    b->g_node_top.bind(M.node_top); b->g_edge_top.bind(M.edge_top); b->g_leaf.bind(M.leaf); b->g_kind.bind(M.kind);
+    b->g_fault.bind(M.fault); b->g_sims.bind(M.sims_done); M.G = n; M.node_cap = node_cap; M.edge_cap = (uint32_t)ecap;
+    HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_init<t.NL, t.W>), c, n, t.CC, b->soa, M); });
+    HIPCHK(hipGetLastError());
+    b->g_has = true; b->g_max_sims = max_sims; b->g_tree_live = true;
+    return TAFL_OK;
+}
+
+int tafl_gmcts_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, double c_puct, uint32_t n_sims, uint32_t* out_waiting) {
+    if (!b || !b->g_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_step: tafl_gmcts_begin first");
+    if (n_sims > b->g_max_sims) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_step: n_sims exceeds the reserved simulations");
+    if ((priors == nullptr) != (values == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_step: priors and values go together");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    HIPCHK(hipSetDevice(c->device));
+    const float* dp = priors; const float* dv = values;
+    if (priors && !in_is_device) {
+        NEED(b->g_priors, sizeof(float) * (size_t)n * A); NEED(b->g_values, sizeof(float) * (size_t)n);
+        HIPCHK(hipMemcpyAsync(b->g_priors.p, priors, sizeof(float) * (size_t)n * A, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(b->g_values.p, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        dp = b->g_priors.as<const float>(); dv = b->g_values.as<const float>();
+    }
+    unsigned long long* st = b->g_stats.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, dp, dv, A, c_puct, n_sims, st); });
+    HIPCHK(hipGetLastError());
+    if (out_waiting) {
+        unsigned long long w = 0;
+        HIPCHK(hipMemcpyAsync(&w, st + GS_WAITING, sizeof w, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        *out_waiting = (uint32_t)w;
+    }
+    return TAFL_OK;
+}
+
+int tafl_gmcts_leaves(tafl_batch* b, uint8_t* boards, uint8_t* sides, uint8_t* waiting, int out_is_device) {
+    if (!b || !b->g_has || !boards || !sides || !waiting) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_leaves: bad argument");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t total = (size_t)n * c->n * c->n;
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t *db, *ds, *dw;
+    STAGED(db, b->g_boards, boards, total, out_is_device);
+    STAGED(ds, b->g_sides, sides, n, out_is_device);
+    STAGED(dw, b->g_wait, waiting, n, out_is_device);
+    dispatch<BATCH, false>(c, [&](auto t) { hipLaunchKernelGGL((k_gmcts_leaves<t.NL, t.W>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, t.CC, b->gmem, db, ds, dw); });
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        COPY_OUT(boards, db, total, c->stream);
+        COPY_OUT(sides, ds, n, c->stream);
+        COPY_OUT(waiting, dw, n, c->stream);
+    }
+    return sync_ok(c);
+}
+
+int tafl_gmcts_root_children(tafl_batch* b, tafl_root_child* out, uint32_t max_children, uint32_t* out_n) {
+    if (!b || !b->g_has || !out || !out_n || max_children == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_root_children: bad argument");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    HIPCHK(hipSetDevice(c->device));
+    NEED(b->children, sizeof(tafl_root_child) * (size_t)n * max_children); NEED(b->children_n, sizeof(uint32_t) * n);
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_root_children<t.NL, t.W>), c, n, t.CC, b->gmem, b->children.as<tafl_root_child>(), max_children, b->children_n.as<uint32_t>()); });
+    HIPCHK(hipGetLastError());
+    COPY_OUT(out, b->children.p, (size_t)n * max_children, c->stream);
+    COPY_OUT(out_n, b->children_n.p, n, c->stream);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (uint32_t g = 0; g < n; ++g) if (out_n[g] > max_children) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_root_children: max_children too small");
+    return TAFL_OK;
+}
+
+static int gmcts_dense(tafl_batch* b, uint32_t* visits, double* probs, double temp, int out_is_device, uint64_t tie_seed = 0, uint64_t game_id_base = 0) {
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c); const size_t count = (size_t)n * A;
+    HIPCHK(hipSetDevice(c->device));
+    uint32_t* dv; double* dp;
+    STAGED(dv, b->visits, visits, count, out_is_device);
+    STAGED(dp, b->policy, probs, count, out_is_device);
+    if (dv) HIPCHK(hipMemsetAsync(dv, 0, sizeof(uint32_t) * count, c->stream));
+    if (dp) HIPCHK(hipMemsetAsync(dp, 0, sizeof(double) * count, c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_root_dense<t.NL, t.W>), c, n, t.CC, b->gmem, dv, dp, A, temp == 0.0 ? 1 : 0, temp == 0.0 ? 1.0 : 1.0 / temp, tie_seed, game_id_base); });
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        COPY_OUT(visits, dv, count, c->stream);
+        COPY_OUT(probs, dp, count, c->stream);
+    }
+    return sync_ok(c);
+}
+int tafl_gmcts_root_visits(tafl_batch* b, uint32_t* out, int out_is_device) {
+    if (!b || !b->g_has || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_root_visits: bad argument");
+    return gmcts_dense(b, out, nullptr, 1.0, out_is_device);
+}
+int tafl_gmcts_policy_ex(tafl_batch* b, double temp, uint64_t tie_seed, uint64_t game_id_base, double* out, int out_is_device) {
+    if (!b || !b->g_has || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_policy: bad argument");
+    if (!(temp >= 0.0)) return fail(TAFL_ERR_INVALID_ARG, "temp must be >= 0");
+    return gmcts_dense(b, nullptr, out, temp, out_is_device, tie_seed, game_id_base);
+}
+int tafl_gmcts_policy(tafl_batch* b, double temp, double* out, int out_is_device) { return tafl_gmcts_policy_ex(b, temp, 0, 0, out, out_is_device); }
+
+// play + re-root of the retained guided tree (tree_advance)
+int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects) {
+    if (!b || !b->g_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: tafl_gmcts_begin first");
+    if (const int rc = join_search(b)) return rc;
+    const bool live = b->g_tree_live;
+    if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: actions == NULL needs a retained tree");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    GuidedMem& M = b->gmem;
+    return tree_advance(b, "tafl_gmcts_advance", b->g_edges, b->g_edges_alt, b->g_idmap, M.node_cap, actions, out_plays, out_effects,
+        [&](const uint32_t* acts, uint32_t A, tafl_play* dplays, tafl_effects* deff, uint32_t* bad) {
+            dispatch<BATCH, false>(c, [&](auto t) {
+                LAUNCH_PER_GAME((k_gmcts_advance<t.NL, t.W>), c, b->n, t.CC, M, b->soa, b->g_edges_alt.as<GEdge>(), b->g_idmap.as<uint32_t>(), acts, live ? 1 : 0, A, dplays, deff, bad); });
+        },
+        [&] { b->g_edges.bind(M.edges); b->g_tree_live = true; b->tree_live = false; });                      // (the rollout-mode tree belongs to the states before the play)
+}
+
+int tafl_gmcts_tree_nodes(tafl_batch* b, uint32_t* out) {
+    if (!b || !out) return fail(TAFL_ERR_INVALID_ARG, "null argument");
+    if (!b->g_has || !b->g_tree_live) { memset(out, 0, sizeof(uint32_t) * b->n); return TAFL_OK; }
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    COPY_OUT(out, b->gmem.node_top, b->n, c->stream);
+    return sync_ok(c);
+}
+
+int tafl_gmcts_get_stats(tafl_batch* b, tafl_gmcts_stats* out) {
+    if (!b || !b->g_has || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_get_stats: bad argument");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[GS_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->g_stats.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memset(out, 0, sizeof *out);
+    out->sims = h[GS_SIMS]; out->predicts = h[GS_PREDICTS]; out->terminal_hits = h[GS_TERMINAL]; out->faults = h[GS_FAULTS];
+    out->select_depth_sum = h[GS_DEPTH]; out->waiting = h[GS_WAITING];
+    return TAFL_OK;
+}
+
+}  // extern "C"

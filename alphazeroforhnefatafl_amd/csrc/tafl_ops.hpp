@@ -1,5 +1,5 @@
 // tafl_ops.hpp — per-game operations behind the C-ABI entry points, written once as
-// __host__ __device__ functions: the HIP kernels (tafl_capi.hip) run them one game per lane,
+// __host__ __device__ functions: the HIP kernels (tafl_core.hip, tafl_mcts.hip) run them one game per lane,
 // tests/hostsim runs the identical code in a CPU loop for differential testing against the oracle.
 //
 // MCTS: the arithmetic of src/mcts.py:55-136 (select :104-123, expand :83-102, backup :127-136)

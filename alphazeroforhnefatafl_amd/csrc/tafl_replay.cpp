@@ -15,7 +15,7 @@
 #include <vector>
 #include "../../include/taflhip.h"
 
-int tafl_fail_(int code, const char* msg);      // tafl_capi.hip: sets the message tafl_last_error() returns
+int tafl_fail_(int code, const char* msg);      // tafl_core.hip: sets the message tafl_last_error() returns
 
 namespace {
 

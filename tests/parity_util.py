@@ -458,7 +458,7 @@ def state_field(states, n, name):
 
 
 def search_partitions(n, parts, block=64):
-    """[(g0, g1)] of the stream partitions a two-kernel search of n games is cut into: the rule of mcts_begin (tafl_capi.hip): the
+    """[(g0, g1)] of the stream partitions a two-kernel search of n games is cut into: the rule of search_partition (tafl_mcts.hip): the
     batch's waves of `block` games are dealt out in order, the first `waves % parts` partitions get one more."""
     waves = (n + block - 1) // block
     parts = max(1, min(parts, waves))

@@ -2,8 +2,7 @@
 """In-kernel section timers of the playout loop ("Where a ply goes").
 
 Needs a PROFILING build of the library (never the product build):
-  cd alphazeroforhnefatafl_amd/csrc && hipcc -O3 -std=c++17 --offload-arch=gfx950 -fPIC -ffp-contract=off -fno-fast-math \
-      -mllvm --amdgpu-sched-strategy=max-ilp -DTAFL_PROF -shared -o /tmp/libtaflhip_prof.so tafl_capi.hip tafl_replay.cpp
+  make -C alphazeroforhnefatafl_amd/csrc profile-lib        (-DTAFL_PROF, all parts as one translation unit, to /tmp/libtaflhip_prof.so)
   TAFLHIP_PROF_LIB=/tmp/libtaflhip_prof.so python tools/profile_sections.py [c11|b7|c13]
 Sections are bracketed by s_memtime reads behind scheduling barriers (TAFL_PROF_* in tafl_bits.hpp), one lane per wave adding into
 its workgroup's row; two empty sections give the cost of a mark.  The optimiser still moves straight-line code across marks, so
