@@ -7,7 +7,7 @@ from . import abi
 from .abi import Ruleset, boards, rules
 
 __all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples",
-           "play_episodes"]
+           "play_episodes", "play_guided_episodes"]
 
 
 def __getattr__(name):
@@ -18,9 +18,9 @@ def __getattr__(name):
     if name in ("MCTS", "MCTSArgs", "GuidedMCTS"):
         from . import mcts
         return getattr(mcts, name)
-    if name == "play_episodes":
+    if name in ("play_episodes", "play_guided_episodes"):
         from . import selfplay
-        return selfplay.play_episodes
+        return getattr(selfplay, name)
     if name == "BatchedGame":
         from . import game
         return game.BatchedGame

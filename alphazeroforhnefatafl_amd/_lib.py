@@ -80,6 +80,9 @@ SYMBOLS = [
     ("tafl_gmcts_begin_ex", _i32, [_vp, _u32, _u32, _u32]),
     ("tafl_gmcts_advance", _i32, [_vp, _P(_u32), _P(TaflPlay), _P(TaflEffects)]),
     ("tafl_gmcts_tree_nodes", _i32, [_vp, _P(_u32)]),
+    ("tafl_gselfplay_begin", _i32, [_vp, _u32, _u32, _dbl, _P(TaflSelfplayOpts), _u32, _u64, _vp]),
+    ("tafl_gselfplay_step", _i32, [_vp, _vp, _vp, _i32, _P(_u32)]),
+    ("tafl_gselfplay_end", _i32, [_vp, _P(TaflPlay), _P(_u32)]),
     ("tafl_replay_append", _i32, [C.c_char_p, _P(_u8), _u8, _P(_u8), _u32, _u8, _u8, _u64]),
     ("tafl_replay_append_batch", _i32, [C.c_char_p, _P(_u8), _u8, _u32, _P(_u8), _P(_u32), _P(_u8), _P(_u8), _u64]),
     ("tafl_replay_read", _i32, [C.c_char_p, _u8, _u32, _P(_u8), _P(_u8), _u32, _P(_u32), _P(_u8), _P(_u8), _P(_u32)]),

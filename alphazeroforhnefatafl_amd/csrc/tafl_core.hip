@@ -248,6 +248,7 @@ static void drain_spans(tafl_ctx* c) {
 static int batch_write(tafl_batch* b) {
     if (const int rc = join_search(b)) return rc;
     b->tree_live = false; b->g_tree_live = false;
+    b->gsp_active = false;                                   // (and close a guided self-play run: it plays on from the states it wrote)
     return TAFL_OK;
 }
 

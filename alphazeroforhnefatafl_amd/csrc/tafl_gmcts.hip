@@ -122,6 +122,58 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_advance(Consts<NL> C, Guid
     if (eff) eff[g] = e;
 }
 
+// guided self-play at each game's own pace (tafl_gselfplay_*): one game per lane.  k_gselfplay_step is k_gmcts_step
+// with the move made in the same launch: the lane that owns a game whose search is complete chooses, records, plays and begins the next search.
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_init(Consts<NL> C, const Quad* soa, GuidedMem M, GSelfPlay sp) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    DState<NL> st; StateIO<NL>::load_soa(soa, M.G, g, st);
+    Guided<NL, W>::selfplay_init(M, g, st, sp);
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_step(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                               uint32_t n_sims, GSelfPlay sp, SelfPlayRec rec, unsigned long long* stats) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::selfplay_step(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, rec, C, gs);
+    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
+    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
+    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
+    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
+    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
+    if (M.kind[g] == 1) atomicAdd(&stats[GS_WAITING], 1ull);
+}
+
+// the arena of a search from fresh roots: max_sims + 1 nodes and (max_sims + 1) x edges_per_node edges per game; the guided stats are zeroed
+static int gmcts_arena(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, const char* name) {
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
+    const uint32_t node_cap = max_sims + 1;
+    const unsigned long long ecap = (unsigned long long)node_cap * edges_per_node;
+    if (ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, std::string(name) + ": edge arena too large");
+    NEED(b->g_node_state, sizeof(Quad) * q * node_cap * n); NEED(b->g_hdr, sizeof(GNode) * (size_t)node_cap * n);
+    NEED(b->g_pedge, sizeof(uint32_t) * (size_t)node_cap * n); NEED(b->g_edges, sizeof(GEdge) * (size_t)ecap * n);
+    NEED(b->g_node_top, 4 * (size_t)n); NEED(b->g_edge_top, 4 * (size_t)n); NEED(b->g_leaf, 4 * (size_t)n); NEED(b->g_kind, n); NEED(b->g_fault, n);
+    NEED(b->g_sims, 4 * (size_t)n); NEED(b->g_stats, sizeof(unsigned long long) * GS_COUNT);
+    GuidedMem& M = b->gmem;
+    b->g_node_state.bind(M.node_state); b->g_hdr.bind(M.hdr); b->g_pedge.bind(M.pedge); b->g_edges.bind(M.edges);
+    b->g_node_top.bind(M.node_top); b->g_edge_top.bind(M.edge_top); b->g_leaf.bind(M.leaf); b->g_kind.bind(M.kind);
+    b->g_fault.bind(M.fault); b->g_sims.bind(M.sims_done); M.G = n; M.node_cap = node_cap; M.edge_cap = (uint32_t)ecap;
+    HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
+    return TAFL_OK;
+}
+// the games now waiting for predict(), as the last step kernel counted them
+static int gmcts_waiting(tafl_batch* b, uint32_t* out_waiting) {
+    if (!out_waiting) return TAFL_OK;
+    tafl_ctx* c = b->ctx;
+    unsigned long long w = 0;
+    HIPCHK(hipMemcpyAsync(&w, b->g_stats.as<unsigned long long>() + GS_WAITING, sizeof w, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    *out_waiting = (uint32_t)w;
+    return TAFL_OK;
+}
+
 extern "C" {
 
 int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) { return tafl_gmcts_begin_ex(b, max_sims, edges_per_node, 0); }
@@ -149,7 +201,8 @@ static int gmcts_begin_keep(tafl_batch* b, uint32_t max_sims, uint32_t edges_per
 int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, uint32_t flags) {
     if (!b || max_sims == 0 || edges_per_node == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_begin: bad argument");
     if (flags & ~(uint32_t)TAFL_GMCTS_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: unknown flags");
-    tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    b->gsp_active = false;                                   // (a guided self-play run on this arena is closed)
     HIPCHK(hipSetDevice(c->device));
     if (flags & TAFL_GMCTS_KEEP_TREE) { if (const int rc = join_search(b)) return rc; }
     if ((flags & TAFL_GMCTS_KEEP_TREE) && b->g_has && b->g_tree_live) {
@@ -159,18 +212,8 @@ int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_nod
         return rc;
     }
     b->g_tree_live = false;
-    const uint32_t node_cap = max_sims + 1;
-    const unsigned long long ecap = (unsigned long long)node_cap * edges_per_node;
-    if (ecap > 0xFFFFFFFFull) return fail(TAFL_ERR_CAPACITY, "tafl_gmcts_begin: edge arena too large");
-    NEED(b->g_node_state, sizeof(Quad) * q * node_cap * n); NEED(b->g_hdr, sizeof(GNode) * (size_t)node_cap * n);
-    NEED(b->g_pedge, sizeof(uint32_t) * (size_t)node_cap * n); NEED(b->g_edges, sizeof(GEdge) * (size_t)ecap * n);
-    NEED(b->g_node_top, 4 * (size_t)n); NEED(b->g_edge_top, 4 * (size_t)n); NEED(b->g_leaf, 4 * (size_t)n); NEED(b->g_kind, n); NEED(b->g_fault, n);
-    NEED(b->g_sims, 4 * (size_t)n); NEED(b->g_stats, sizeof(unsigned long long) * GS_COUNT);
+    if (const int rc = gmcts_arena(b, max_sims, edges_per_node, "tafl_gmcts_begin")) return rc;
     GuidedMem& M = b->gmem;
-    b->g_node_state.bind(M.node_state); b->g_hdr.bind(M.hdr); b->g_pedge.bind(M.pedge); b->g_edges.bind(M.edges);
-    b->g_node_top.bind(M.node_top); b->g_edge_top.bind(M.edge_top); b->g_leaf.bind(M.leaf); b->g_kind.bind(M.kind);
-    b->g_fault.bind(M.fault); b->g_sims.bind(M.sims_done); M.G = n; M.node_cap = node_cap; M.edge_cap = (uint32_t)ecap;
-    HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_init<t.NL, t.W>), c, n, t.CC, b->soa, M); });
     HIPCHK(hipGetLastError());
     b->g_has = true; b->g_max_sims = max_sims; b->g_tree_live = true;
@@ -194,13 +237,7 @@ int tafl_gmcts_step(tafl_batch* b, const float* priors, const float* values, int
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, dp, dv, A, c_puct, n_sims, st); });
     HIPCHK(hipGetLastError());
-    if (out_waiting) {
-        unsigned long long w = 0;
-        HIPCHK(hipMemcpyAsync(&w, st + GS_WAITING, sizeof w, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        *out_waiting = (uint32_t)w;
-    }
-    return TAFL_OK;
+    return gmcts_waiting(b, out_waiting);
 }
 
 int tafl_gmcts_leaves(tafl_batch* b, uint8_t* boards, uint8_t* sides, uint8_t* waiting, int out_is_device) {
@@ -266,6 +303,7 @@ int tafl_gmcts_policy(tafl_batch* b, double temp, double* out, int out_is_device
 int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects) {
     if (!b || !b->g_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: tafl_gmcts_begin first");
     if (const int rc = join_search(b)) return rc;
+    b->gsp_active = false;
     const bool live = b->g_tree_live;
     if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: actions == NULL needs a retained tree");
     tafl_ctx* c = b->ctx;
@@ -298,6 +336,76 @@ int tafl_gmcts_get_stats(tafl_batch* b, tafl_gmcts_stats* out) {
     memset(out, 0, sizeof *out);
     out->sims = h[GS_SIMS]; out->predicts = h[GS_PREDICTS]; out->terminal_hits = h[GS_TERMINAL]; out->faults = h[GS_FAULTS];
     out->select_depth_sum = h[GS_DEPTH]; out->waiting = h[GS_WAITING];
+    return TAFL_OK;
+}
+
+// ---- guided self-play at each game's own pace -----------------------------------------------------------------
+static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    unsigned long long* st = b->g_stats.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st); });
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
+                         tafl_examples* ex) {
+    if (!b || !o || n_sims == 0 || edges_per_node == 0 || n_moves == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: bad argument");
+    if (n_sims > 0xFFFFu) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: n_sims must be below 65536 (Nsa is stored in 16 bits)");
+    if (o->flags != 0 || o->_reserved[0] != 0 || o->_reserved[1] != 0 || o->_reserved[2] != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_opts: flags and reserved words must be 0");
+    if ((unsigned long long)o->move_base + n_moves > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: move_base + n_moves exceeds 32 bits");
+    if (ex && (ex->n_games != b->n || ex->ctx->device != b->ctx->device || ex->ctx->n != b->ctx->n))
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: the examples object was created for another batch size, board or device");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    b->gsp_active = false;
+    if (const int rc = join_search(b)) return rc;
+    if (ex) { HIPCHK(hipSetDevice(ex->ctx->device)); HIPCHK(hipStreamSynchronize(ex->ctx->stream)); }      // (clears and gathers of another context's stream)
+    HIPCHK(hipSetDevice(c->device));
+    b->tree_live = false; b->g_tree_live = false; b->ran = false;      // the run plays away from the roots of both retained trees
+    if (const int rc = gmcts_arena(b, n_sims, edges_per_node, "tafl_gselfplay_begin")) return rc;
+    NEED(b->gsp_moves_done, sizeof(uint32_t) * (size_t)n); NEED(b->gsp_plays, sizeof(tafl_play) * (size_t)n * n_moves);
+    b->gsp_moves_done.bind(b->gsp.moves_done); b->gsp_plays.bind(b->gsp.plays); b->gsp.n_moves = n_moves;
+    b->gsp_rec = SelfPlayRec{};
+    if (ex) b->gsp_rec.ex = ex->mem;
+    b->gsp_rec.sample_seed = o->sample_seed; b->gsp_rec.game_id_base = game_id_base; b->gsp_rec.temp_moves = o->temp_moves; b->gsp_rec.move_base = o->move_base;
+    b->gsp_sims = n_sims; b->gsp_cpuct = c_puct;
+    HIPCHK(hipMemsetAsync(b->gsp_plays.p, 0, sizeof(tafl_play) * (size_t)n * n_moves, c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_init<t.NL, t.W>), c, n, t.CC, b->soa, b->gmem, b->gsp); });
+    HIPCHK(hipGetLastError());
+    b->g_has = true; b->g_max_sims = n_sims;
+    if (const int rc = gselfplay_launch(b, nullptr, nullptr)) return rc;      // the first round: every live root waits for its evaluation
+    b->gsp_has = true; b->gsp_active = true; b->gsp_first = true;
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, uint32_t* out_waiting) {
+    if (!b || !b->gsp_active) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: no run is open on this batch (tafl_gselfplay_begin first; a write to the batch states closes a run)");
+    if ((priors == nullptr) != (values == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: priors and values go together");
+    if (b->gsp_first != (priors == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: the first step after tafl_gselfplay_begin, and only that one, takes priors = values = NULL");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    HIPCHK(hipSetDevice(c->device));
+    if (b->gsp_first) { b->gsp_first = false; return gmcts_waiting(b, out_waiting); }      // (tafl_gselfplay_begin ran that round)
+    const float* dp = priors; const float* dv = values;
+    if (!in_is_device) {
+        NEED(b->g_priors, sizeof(float) * (size_t)n * A); NEED(b->g_values, sizeof(float) * (size_t)n);
+        HIPCHK(hipMemcpyAsync(b->g_priors.p, priors, sizeof(float) * (size_t)n * A, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(b->g_values.p, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        dp = b->g_priors.as<const float>(); dv = b->g_values.as<const float>();
+    }
+    if (const int rc = gselfplay_launch(b, dp, dv)) return rc;
+    return gmcts_waiting(b, out_waiting);
+}
+
+int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves) {
+    if (!b || !b->gsp_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_end: tafl_gselfplay_begin first");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    b->gsp_active = false;
+    HIPCHK(hipSetDevice(c->device));
+    COPY_OUT(out_plays, b->gsp_plays.p, (size_t)n * b->gsp.n_moves, c->stream);
+    COPY_OUT(out_moves, b->gsp_moves_done.p, n, c->stream);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (out_moves) for (uint32_t g = 0; g < n; ++g) out_moves[g] &= ~kGspStopped;
     return TAFL_OK;
 }
 

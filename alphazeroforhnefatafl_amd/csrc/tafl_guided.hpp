@@ -48,6 +48,13 @@ struct GuidedMem {
     uint32_t G, node_cap, edge_cap;
 };
 struct GuidedStats { uint32_t sims, predicts, terminal_hits, faults, depth; };
+// per-run state of a guided self-play run (tafl_gselfplay_*)
+constexpr uint32_t kGspStopped = 0x80000000u;    // GSelfPlay::moves_done: the game makes no further move in this run
+struct GSelfPlay {
+    uint32_t* moves_done;        // [G] moves made in this run | kGspStopped
+    tafl_play* plays;            // [m * G + g] the play of move m (all-zero: not made)
+    uint32_t n_moves;
+};
 
 template <int NL, int W>
 struct Guided {
@@ -280,6 +287,91 @@ struct Guided {
             ++k;
         }
         return k;
+    }
+
+    // ---- guided self-play at each game's own pace (tafl_gselfplay_*) -----------------------------------------
+    // Ops::selfplay_pick over the root's edge block: k = mulhi(r, N) with N = sum of Nsa, and the play is the first edge in ascending action
+    // order whose running sum of Nsa exceeds k.  The block holds one edge per LEGAL move, so unvisited edges (n == 0) lie between the
+    // visited ones; they add nothing to the running sum and are never drawn.  Returns the index inside the block.  Integers only.
+    static TAFL_HD uint32_t selfplay_pick(const GEdge* eb, uint32_t n_legal, uint32_t N, uint32_t r) {
+        const uint32_t k = E::mulhi(r, N);
+        uint32_t run = 0, last = 0;
+        for (uint32_t j = 0; j < n_legal; ++j) { const uint32_t v = eb[j].n; if (v == 0) continue; run += v; last = j; if (run > k) return j; }
+        return last;
+    }
+    // Ops::example_record over the root's edge block: appends the example of the move game g is about to make from `st` (m visited edges,
+    // play = edge `pick`).  The action is in the edge: no child header is read.
+    static TAFL_HD void example_record(uint32_t g, const ExamplesMem& X, const S& st, const GEdge* eb, uint32_t n_legal, uint32_t m, uint32_t pick, uint32_t move_no, const K& C) {
+        const uint32_t j = X.len[g];
+        if (j >= X.max_moves) { TAFL_COUNT_ADD(&X.counters[EX_DROPPED], 1); return; }
+        const size_t e = (size_t)j * X.G + g;
+        uint32_t w = 0, t = 0;
+        for (uint32_t r = 0; r < C.n; ++r)
+            for (uint32_t c = 0; c < C.n; ++c) {
+                w |= O::board_byte(st, r, c, C) << (8u * (t & 3u));
+                if ((t & 3u) == 3u) { X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w; w = 0; }
+                ++t;
+            }
+        if (t & 3u) X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w;
+        const bool over = m > X.K;
+        uint32_t total = 0;
+        if (!over)
+            for (uint32_t i = 0, k = 0; i < n_legal; ++i) {
+                const uint32_t v = eb[i].n;
+                if (v == 0) continue;
+                X.pol[((size_t)j * X.K + k) * X.G + g] = eb[i].action | (v << 16); total += v; ++k;
+            }
+        if (over) TAFL_COUNT_ADD(&X.counters[EX_OVERFLOWED], 1);
+        X.info[e] = (over ? kExOverflow : m) | (((st.flags & TAFL_F_SIDE) ? (uint32_t)TAFL_DEFENDER : (uint32_t)TAFL_ATTACKER) << 16);
+        X.played[e] = eb[pick].action | (total << 16); X.move_no[e] = move_no; X.z[e] = 0.0f; X.fin[e] = 0;
+        X.len[g] = j + 1u;
+    }
+    // the start of a run for game g: a fresh root from its batch state; a game that is over makes no move
+    static TAFL_HD void selfplay_init(const GuidedMem& M, uint32_t g, const S& root, const GSelfPlay& sp) {
+        init_game(M, g, root);
+        const bool over = TAFL_F_STATUS(root.flags) != TAFL_STATUS_ONGOING;
+        if (over) M.kind[g] = 3;
+        sp.moves_done[g] = over ? kGspStopped : 0u;
+    }
+    // One round of the run for game g: `step`; if that completes the game's search, the play of move M = move_base + moves made is chosen
+    // (the most visited edge, first maximum, or for M < temp_moves the draw of selfplay_pick), its example is appended, the play is made on
+    // the batch state `soa`, and - while the game goes on and has moves left - the next search begins from a fresh root, which waits for
+    // its evaluation at once.  The state after the play is the record of the played edge's child, which `step` made with Engine::apply
+    // (= do_valid_play) when the edge was first visited.  A game that faults, is over, has no visited root edge or has made n_moves moves stops.
+    static TAFL_HD void selfplay_step(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                      const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs) {
+        uint32_t md = sp.moves_done[g];
+        if (md & kGspStopped) return;
+        // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
+        for (;;) {
+            step(M, g, priors, value, A, c_puct, n_sims, C, gs);
+            if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
+            if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
+            const GNode h = M.hdr[g];
+            const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+            uint32_t best = 0, pick = 0, total = 0, m = 0;
+            if (h.expanded)
+                for (uint32_t j = 0; j < h.n_legal; ++j) {
+                    const uint32_t v = eb[j].n;
+                    if (v > best) { best = v; pick = j; }
+                    total += v; m += v != 0u;
+                }
+            if (m == 0) { sp.moves_done[g] = md | kGspStopped; return; }   // (n_sims == 1: the root was evaluated, no edge visited)
+            const uint32_t move_no = rec.move_base + md;
+            if (move_no < rec.temp_moves) pick = selfplay_pick(eb, h.n_legal, total, selfplay_rand(rec.sample_seed, rec.game_id_base + g, move_no));
+            const GEdge pe = eb[pick];
+            S st;
+            if (rec.ex.len) { IO::load_soa(soa, M.G, g, st); example_record(g, rec.ex, st, eb, h.n_legal, m, pick, move_no, C); }
+            IO::load_rec(M.node_state + ((size_t)pe.child * M.G + g) * IO::QUADS, st);
+            IO::store_soa(soa, M.G, g, st);
+            Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;
+            sp.plays[(size_t)md * M.G + g] = O::to_play(mv);
+            md += 1u;
+            if (md >= sp.n_moves || TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { sp.moves_done[g] = md | kGspStopped; return; }
+            sp.moves_done[g] = md;
+            init_game(M, g, st);
+            priors = nullptr;
+        }
     }
 };
 

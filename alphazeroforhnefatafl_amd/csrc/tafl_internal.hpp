@@ -205,6 +205,11 @@ struct tafl_batch {
     // guided MCTS (external evaluator)
     GuidedMem gmem = {}; bool g_has = false; uint32_t g_max_sims = 0;
     DevBuf g_node_state, g_hdr, g_pedge, g_edges, g_node_top, g_edge_top, g_leaf, g_kind, g_fault, g_sims, g_stats, g_priors, g_values, g_boards, g_sides, g_wait;
+    // guided self-play at each game's own pace (tafl_gselfplay_*): the run open on the guided arena; gsp_first: tafl_gselfplay_begin has run
+    // the first round and the first tafl_gselfplay_step reports it; gsp_has: the buffers hold the plays of a run (tafl_gselfplay_end)
+    bool gsp_active = false, gsp_first = false, gsp_has = false;
+    GSelfPlay gsp = {}; SelfPlayRec gsp_rec = {}; uint32_t gsp_sims = 0; double gsp_cpuct = 0.0;
+    DevBuf gsp_moves_done, gsp_plays;
     // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
     // arena and the id map of a re-root; a small read-back buffer
     bool tree_live = false, g_tree_live = false;

@@ -771,7 +771,7 @@ int mcts_begin(tafl_batch* b, const tafl_mcts_params* p, uint64_t game_id_base, 
 int selfplay_finish(tafl_batch* b, int rc, uint32_t n_moves, tafl_play* out_plays) {
     if (rc == TAFL_OK) rc = tafl_mcts_wait(b);
     b->ran = false;                                          // the trees belong to roots that have been played away from
-    b->tree_live = false; b->g_tree_live = false;
+    b->tree_live = false; b->g_tree_live = false; b->gsp_active = false;
     if (rc) return rc;
     if (out_plays) {
         COPY_OUT(out_plays, b->sp_plays.p, (size_t)b->n * n_moves, b->ctx->stream);
@@ -939,7 +939,7 @@ int tafl_mcts_play_best(tafl_batch* b, tafl_play* out_plays, tafl_effects* out_e
     COPY_OUT(out_effects, deff, n, c->stream);
     if (out_plays || out_effects) HIPCHK(hipStreamSynchronize(c->stream));
     b->ran = false;                                   // the tree belongs to the previous roots
-    b->tree_live = false; b->g_tree_live = false;
+    b->tree_live = false; b->g_tree_live = false; b->gsp_active = false;
     return TAFL_OK;
 }
 
@@ -948,6 +948,7 @@ int tafl_mcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_pla
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "null batch");
     int rc = join_search(b);
     if (rc != TAFL_OK) return rc;
+    b->gsp_active = false;
     const bool live = b->tree_live && b->has_mem;
     if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_mcts_advance: actions == NULL needs a retained tree (run a search first)");
     tafl_ctx* c = b->ctx;

@@ -103,6 +103,7 @@ class GameBatch:
     def __init__(self, logic: BatchedGameLogic, n_games: int):
         self.logic = logic
         self.n = n_games
+        self._gsp_moves = 0               # n_moves of the last gselfplay_begin (the size of gselfplay_end's plays)
         self._h = C.c_void_p()
         check(lib().tafl_batch_create(logic._h, n_games, C.byref(self._h)))
         logic._batches.add(self)
@@ -327,6 +328,32 @@ class GameBatch:
         st = TaflGmctsStats()
         check(lib().tafl_gmcts_get_stats(self._h, C.byref(st)))
         return st
+
+    # -- guided self-play at each game's own pace (include/taflhip.h tafl_gselfplay_*) ------------------------------------
+    def gselfplay_begin(self, examples: "Examples | None", n_moves: int, n_sims: int, c_puct: float = 1.0, edges_per_node: int = 256,
+                        game_id_base: int = 0, sample_seed: int = 0, temp_moves: int = 0, move_base: int = 0):
+        """Opens a guided self-play run (tafl_gselfplay_begin): every game, n_moves times, searches n_sims simulations with the caller's
+        evaluator, chooses its play by the rule of selfplay_record, appends the example to `examples` (None: only the plays) and plays
+        it, all inside gselfplay_step.  The first gselfplay_step takes no priors."""
+        o = TaflSelfplayOpts(sample_seed, temp_moves, move_base, 0)
+        check(lib().tafl_gselfplay_begin(self._h, n_sims, edges_per_node, c_puct, C.byref(o), n_moves, game_id_base,
+                                         examples._h if examples is not None else None))
+        self._gsp_moves = n_moves
+
+    def gselfplay_step(self, priors=None, values=None, device: bool = False, want_waiting: bool = True) -> int:
+        """One round of the run: gmcts_step's arguments (the run's c_puct and n_sims).  Returns the games now waiting; 0: the run is complete."""
+        w = C.c_uint32()
+        pp = C.c_void_p(priors) if isinstance(priors, int) else (C.cast(priors, C.c_void_p) if priors is not None else None)
+        pv = C.c_void_p(values) if isinstance(values, int) else (C.cast(values, C.c_void_p) if values is not None else None)
+        check(lib().tafl_gselfplay_step(self._h, pp, pv, int(device), C.byref(w) if want_waiting else None))
+        return w.value
+
+    def gselfplay_end(self, want_plays: bool = True):
+        """Closes the run (tafl_gselfplay_end): (plays [m * n + g], all-zero for a move not made, or None; moves made per game [n])."""
+        plays = (TaflPlay * (self.n * self._gsp_moves))() if want_plays and self._gsp_moves else None
+        moves = (C.c_uint32 * self.n)()
+        check(lib().tafl_gselfplay_end(self._h, plays, moves))
+        return plays, moves
 
     def mcts_play_best(self, want_results: bool = True):
         """Every game plays the most visited root play of its last search, on the device (tafl_mcts_play_best)."""

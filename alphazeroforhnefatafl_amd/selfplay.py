@@ -1,5 +1,6 @@
-"""Self-play episodes that leave their training examples on the device (include/taflhip.h tafl_selfplay_record):
-the executeEpisode loop of alpha-zero-general - the code base the reference's src/mcts.py belongs to - for a whole batch of games."""
+"""Self-play episodes that leave their training examples on the device (include/taflhip.h tafl_selfplay_record and tafl_gselfplay_*,
+DESIGN.md sections 12 and 13): the executeEpisode loop of alpha-zero-general - the code base the reference's src/mcts.py belongs to -
+for a whole batch of games, with random playouts (play_episodes) or the caller's network (play_guided_episodes) as the evaluator."""
 from __future__ import annotations
 
 import ctypes as C
@@ -34,3 +35,26 @@ def play_episodes(batch: GameBatch, examples: Examples, args: MCTSArgs, max_move
     examples.finalize(batch)
     lens, total = examples.counts()
     return lens, total, over
+
+
+def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSArgs, max_moves: int, *, sample_seed: int = 1,
+                         temp_moves: int = 0, edges_per_node: int = 256, device: bool = False, buffers=None):
+    """play_episodes with `nnet` as the evaluator (GuidedMCTS's protocol: nnet.predict_batch(boards, sides, waiting) -> (priors, values);
+    with device=True `buffers` = (boards_ptr, sides_ptr, waiting_ptr) and everything is a device pointer).  One run of `max_moves` moves
+    (tafl_gselfplay_*): every game searches args.numMCTSSims simulations per move at its own pace, so the host loop is leaves -> network
+    -> step until nothing waits, with no read-back per move.  Ends with Examples.finalize.  Returns (examples per game, their sum,
+    games that are over)."""
+    batch.gselfplay_begin(examples, max_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=args.game_id_base,
+                          sample_seed=sample_seed, temp_moves=temp_moves)
+    waiting = batch.gselfplay_step()
+    while waiting:
+        if device:
+            batch.gmcts_leaves(*buffers)
+            priors, values = nnet.predict_batch(*buffers)
+        else:
+            priors, values = nnet.predict_batch(*batch.gmcts_leaves())
+        waiting = batch.gselfplay_step(priors, values, device=device)
+    batch.gselfplay_end(want_plays=False)
+    examples.finalize(batch)
+    lens, total = examples.counts()
+    return lens, total, _games_over(batch)

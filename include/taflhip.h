@@ -511,6 +511,50 @@ int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_nod
 int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_plays, tafl_effects* out_effects);
 int tafl_gmcts_tree_nodes(tafl_batch* b, uint32_t* out);
 
+/* ---- guided self-play at each game's own pace, recording training examples -------------------------------------
+ * The network-guided twin of tafl_selfplay_record: every game, n_moves times, searches n_sims simulations with the CALLER's evaluator,
+ * chooses its play, appends the move's example to `ex`, plays the move on its batch state and starts its next search in the same kernel
+ * launch.  The host loop is  tafl_gselfplay_begin; tafl_gselfplay_step(NULL, NULL); while (waiting) { tafl_gmcts_leaves; network;
+ * tafl_gselfplay_step(priors, values) }; tafl_gselfplay_end  - nothing is read back per move, and a game that finishes a search asks for
+ * its next root's evaluation in the very next round, so the evaluator's batch stays full until games end.  It replaces, per move,
+ * { tafl_gmcts_begin; the step loop; tafl_gmcts_root_visits to the host; a choice on the host; tafl_step }.
+ *
+ * Per game the run is exactly this loop (the evaluator must be a function of the leaf it is shown):
+ *   for m in 0 .. n_moves:
+ *       if the game is over: stop
+ *       fresh root from the batch state                 (tafl_gmcts_begin)
+ *       n_sims simulations of src/mcts.py:55-136        (the arithmetic of tafl_gmcts_step, unchanged)
+ *       choose, record, play
+ * with M = opts->move_base + m, gid = game_id_base + game, the visited root edges (Nsa > 0) in ascending action order, N = sum of their Nsa:
+ *   choose     M >= temp_moves: the most visited edge, first maximum - what tafl_gmcts_advance(actions = NULL) plays.  M < temp_moves:
+ *              r = ply_rand(sim_key(game_key(sample_seed, gid), M), 0), k = (r * N) >> 32, and the play is the first visited edge whose
+ *              running sum of Nsa exceeds k: the word and the rule of tafl_selfplay_record.  No floating point, no dependence on the
+ *              sharding.  A root without a visited edge (n_sims == 1) plays nothing and records nothing, and the game makes no further move.
+ *   record     when ex != NULL, the example of tafl_selfplay_record: the board_to_matrix bytes of the position before the play, the side to
+ *              move, n_children and per visited root edge (action, Nsa), the play's action, move_no = M.  The capacity rules are the same:
+ *              len[g] == max_moves counts tafl_examples_stats.dropped, more than max_children visited edges counts overflowed (n_children =
+ *              0); neither is a fault of the search.  tafl_examples_finalize and tafl_examples_gather are used as they are.
+ *   play       do_valid_play on the batch state.  tafl_gselfplay_end hands out the plays [m * n + g] (all-zero for a move not made; may be
+ *              NULL) and the number of moves each game made [n] (may be NULL).
+ * A game whose arena overflows raises its fault flag as in tafl_gmcts_step (stats.faults), stops searching and moving, and the other
+ * games are not affected.
+ *
+ * tafl_gselfplay_begin joins a search in flight, drops both retained trees, sizes the guided arena as tafl_gmcts_begin(n_sims,
+ *   edges_per_node) does (a fresh root per move, no reuse), zeroes the guided stats and runs the first round; the first tafl_gselfplay_step
+ *   then takes priors = values = NULL and reports the games that wait, exactly like tafl_gmcts_step after tafl_gmcts_begin (every later
+ *   step takes both).  n_sims == 0, n_sims >= 65536, n_moves == 0, or `ex` of another size, board or device: TAFL_ERR_INVALID_ARG;
+ *   non-zero opts->flags or reserved words: TAFL_ERR_UNSUPPORTED.
+ * tafl_gselfplay_step: priors / values / in_is_device as tafl_gmcts_step; c_puct and n_sims are the run's.  out_waiting (may be NULL) == 0
+ *   means the run is complete.  tafl_gmcts_leaves serves the network input unchanged; tafl_gmcts_get_stats covers all searches of the run.
+ * A call that writes the batch states (tafl_batch_reset_fen, tafl_batch_upload, tafl_step, tafl_step_kth, tafl_random_advance,
+ *   tafl_selfplay_run / _record, tafl_mcts_play_best, tafl_mcts_advance, tafl_gmcts_advance), a tafl_gmcts_begin / _begin_ex, or
+ *   tafl_gselfplay_end closes the run: a tafl_gselfplay_step on a closed run fails with TAFL_ERR_INVALID_ARG.  tafl_gselfplay_end may be
+ *   called while games still wait; the moves made so far stand. */
+int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* opts,
+                         uint32_t n_moves, uint64_t game_id_base, tafl_examples* ex);
+int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, uint32_t* out_waiting);
+int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves);
+
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
  * with the comma-separated vector, one line value1, one line value2; every line ends in '\n'.

@@ -1,0 +1,197 @@
+"""Expected values and drivers for the guided self-play tests (include/taflhip.h tafl_gselfplay_*): the oracle loop
+- orc.GameLogic.gmcts, the pick rule and the RNG word restated in tests/examples_util.py, the oracle's do_play - and the loader of the
+host harness tests/hostsim_gselfplay/libhostsim_gselfplay.so (Guided::selfplay_step compiled for the CPU)."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from alphazeroforhnefatafl_amd import abi
+from alphazeroforhnefatafl_amd.abi import TaflPlay, TaflRules, TaflSelfplayOpts, TaflState
+from tests import examples_util as eu
+from tests import parity_util as pu
+from tests.stub_net import matrix_bytes_of, stub_predict
+
+_STUB = {}
+
+
+def stub(matrix_bytes: bytes, side: int, action_size: int, salt: int):
+    """stub_predict, remembered: the oracle loop, the harness and the device runs of one test ask for the same leaves."""
+    key = (matrix_bytes, side, action_size, salt)
+    hit = _STUB.get(key)
+    if hit is None:
+        hit = _STUB[key] = stub_predict(matrix_bytes, side, action_size, salt)
+    return hit
+
+
+def stub_rows(boards, sides, waiting, n, side_len, action_size, salts):
+    """nnet.predict for every waiting game: (priors float32 [n, A], values float32 [n]) as numpy arrays."""
+    nn = side_len * side_len
+    raw = bytes(boards)
+    pri, val = np.zeros((n, action_size), np.float32), np.zeros(n, np.float32)
+    for g in range(n):
+        if waiting[g]:
+            pri[g], val[g] = stub(raw[g * nn:(g + 1) * nn], int(sides[g]), action_size, salts[g])
+    return pri, val
+
+
+def fptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_float))
+
+
+def start_states(orc, lg, rules, fen, wb, G, modulus, seed=21):
+    """Game i = the start position advanced by (7 i) mod `modulus` random plies (modulus 0: the start position)."""
+    base = orc.GameState(fen, rules.starting_side, wb)
+    return (TaflState * G)(*[(lg.random_advance(base, seed, g, (7 * g) % modulus) if modulus else base).to_abi() for g in range(G)])
+
+
+class Run:
+    """What a run leaves: plays[m][g] as 4-tuples, final states (bytes per game), moves made per game, examples per game
+    (examples_util.Example.fields() tuples), sims."""
+
+    def __init__(self, G, n_moves):
+        self.plays = [[(0, 0, 0, 0)] * G for _ in range(n_moves)]
+        self.states, self.moves, self.examples, self.sims = [None] * G, [0] * G, [[] for _ in range(G)], 0
+
+
+def oracle_run(orc, lg, states, wb, S, c_puct, salts, n_moves, sample_seed, temp_moves, move_base=0, base=0, games=None):
+    """The loop of include/taflhip.h on the oracle, per game: gmcts from a fresh root, the pick, the example, do_play."""
+    G = len(states)
+    n = states[0].side_len
+    A = abi.action_size(n)
+    out = Run(G, n_moves)
+    for g in (range(G) if games is None else games):
+        st = orc.GameState.from_abi(states[g], wb)
+        for m in range(n_moves):
+            if st.to_abi().status != abi.ONGOING:
+                break
+            kids, _ns, _pri, _cnt = lg.gmcts(st, S, c_puct, lambda s, g=g: stub(matrix_bytes_of(s.board_to_matrix()), int(s.side_to_play), A, salts[g]), wb)
+            out.sims += S
+            vs = [v for (_p, _a, v, _q) in kids]
+            if not vs:
+                break
+            M = move_base + m
+            j = eu.pick_rule(vs, eu.sample_word(sample_seed, base + g, M)) if M < temp_moves else vs.index(max(vs))
+            e = eu.Example()
+            e.board, e.side = st.board_to_matrix(), st.to_abi().side_to_play
+            e.actions, e.visits, e.played, e.move_no = [a for (_p, a, _v, _q) in kids], vs, kids[j][1], M
+            out.examples[g].append(e.fields())
+            play = abi.action_decode(n, kids[j][1])
+            code, st, _eff = lg.do_play(play, st)
+            assert code == 0, (g, m, code)
+            out.plays[m][g] = pu.play_tuple4(play)
+            out.moves[g] = m + 1
+        out.states[g] = bytes(st.to_abi())
+    return out
+
+
+# ---- the host harness ---------------------------------------------------------------------------------------------------------
+_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_gselfplay")
+_LIB = None
+
+
+def hlib():
+    global _LIB
+    if _LIB is None:
+        subprocess.check_call(["make", "-C", _HERE, "-s", "libhostsim_gselfplay.so"])
+        L = C.CDLL(os.path.join(_HERE, "libhostsim_gselfplay.so"))
+        P, u8, u32, u64, vp = C.POINTER, C.c_uint8, C.c_uint32, C.c_uint64, C.c_void_p
+        L.hsg_ex_new.restype = vp; L.hsg_ex_new.argtypes = [u32, u8, u32, u32]
+        L.hsg_ex_free.restype = None; L.hsg_ex_free.argtypes = [vp]
+        L.hsg_ex_counts.restype = None; L.hsg_ex_counts.argtypes = [vp, P(u32), P(u64)]
+        L.hsg_ex_example.restype = C.c_int; L.hsg_ex_example.argtypes = [vp, u32, P(u32), P(u8), P(u32), P(u32)]
+        L.hsg_begin.restype = vp
+        L.hsg_begin.argtypes = [P(TaflRules), u8, u32, P(TaflState), u32, u32, u32, C.c_double, P(TaflSelfplayOpts), u32, u64, vp]
+        L.hsg_free.restype = None; L.hsg_free.argtypes = [vp]
+        L.hsg_step.restype = u32; L.hsg_step.argtypes = [vp, P(C.c_float), P(C.c_float)]
+        L.hsg_leaves.restype = None; L.hsg_leaves.argtypes = [vp, P(u8), P(u8), P(u8)]
+        L.hsg_end.restype = None; L.hsg_end.argtypes = [vp, P(TaflState), P(TaflPlay), P(u32), P(u64), P(u8)]
+        L.hsg_pick_many.restype = None; L.hsg_pick_many.argtypes = [P(u32), u32, P(u32), u32, P(u32)]
+        L.hsg_rand.restype = u32; L.hsg_rand.argtypes = [u64, u64, u32]
+        _LIB = L
+    return _LIB
+
+
+class HostExamples:
+    """tafl_examples on host memory."""
+
+    def __init__(self, n, G, max_moves, K):
+        self.n, self.G, self.max_moves, self.K = n, G, max_moves, K
+        self.h = hlib().hsg_ex_new(G, n, max_moves, K)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            hlib().hsg_ex_free(self.h)
+            self.h = None
+
+    def counts(self):
+        ln, ct = (C.c_uint32 * self.G)(), (C.c_uint64 * 4)()
+        hlib().hsg_ex_counts(self.h, ln, ct)
+        return list(ln), {"dropped": ct[0], "overflowed": ct[1], "bad_index": ct[2]}
+
+    def example(self, j, g):
+        """(Example.fields() tuple, overflow) of example (j, g)."""
+        out5, board = (C.c_uint32 * 5)(), (C.c_uint8 * (self.n * self.n))()
+        acts, vis = (C.c_uint32 * self.K)(), (C.c_uint32 * self.K)()
+        assert hlib().hsg_ex_example(self.h, j * self.G + g, out5, board, acts, vis) == 0, (j, g)
+        k = out5[0]
+        rows = [list(board[r * self.n:(r + 1) * self.n]) for r in range(self.n)]
+        return (rows, out5[1], list(acts[:k]), list(vis[:k]), out5[3], out5[4]), out5[2]
+
+    def all(self):
+        """(examples per game as fields tuples, overflow marks per game)."""
+        lens, _ = self.counts()
+        got = [[self.example(j, g) for j in range(min(lens[g], self.max_moves))] for g in range(self.G)]
+        return [[f for f, _ in row] for row in got], [[o for _, o in row] for row in got]
+
+
+def host_run(rules, n, wb, states, S, c_puct, salts, n_moves, sample_seed, temp_moves, ex=None, move_base=0, base=0, edges_per_node=256):
+    """tafl_gselfplay_begin / the step loop / tafl_gselfplay_end on the harness, with the stub network.  Returns (Run, faults [G], rounds);
+    Run.examples is left empty (read them from `ex`)."""
+    L = hlib()
+    G, A = len(states), abi.action_size(n)
+    rc = rules.to_c() if isinstance(rules, abi.Ruleset) else rules
+    o = TaflSelfplayOpts(sample_seed, temp_moves, move_base, 0)
+    h = L.hsg_begin(C.byref(rc), n, wb, states, G, S, edges_per_node, c_puct, C.byref(o), n_moves, base, ex.h if ex is not None else None)
+    assert h
+    try:
+        boards, sides, waiting = (C.c_uint8 * (G * n * n))(), (C.c_uint8 * G)(), (C.c_uint8 * G)()
+        L.hsg_leaves(h, boards, sides, waiting)
+        w, rounds = sum(waiting), 0
+        while w:
+            pri, val = stub_rows(boards, sides, waiting, G, n, A, salts)
+            w = L.hsg_step(h, fptr(pri), fptr(val))
+            L.hsg_leaves(h, boards, sides, waiting)
+            assert sum(waiting) == w
+            rounds += 1
+        st, plays, moves, cnt, faults = (TaflState * G)(), (TaflPlay * (G * n_moves))(), (C.c_uint32 * G)(), (C.c_uint64 * 4)(), (C.c_uint8 * G)()
+        L.hsg_end(h, st, plays, moves, cnt, faults)
+    finally:
+        L.hsg_free(h)
+    out = Run(G, n_moves)
+    out.plays = [[pu.play_tuple4(plays[m * G + g]) for g in range(G)] for m in range(n_moves)]
+    out.states, out.moves, out.sims = [bytes(st[g]) for g in range(G)], list(moves), cnt[0]
+    out.abi_states, out.stat_faults = st, cnt[3]
+    return out, list(faults), rounds
+
+
+def fates(states_before, run):
+    """(games over at the start, games that ended during the run, games still going after it)."""
+    G = len(states_before)
+    over0 = [g for g in range(G) if states_before[g].status != abi.ONGOING]
+    after = [TaflState.from_buffer_copy(run.states[g]).status for g in range(G)]
+    ended = [g for g in range(G) if g not in over0 and after[g] != abi.ONGOING]
+    going = [g for g in range(G) if after[g] == abi.ONGOING]
+    return over0, ended, going
+
+
+def assert_same_run(got: Run, want: Run, got_examples, games=None, where=""):
+    G = len(want.states)
+    for g in (range(G) if games is None else games):
+        assert [row[g] for row in got.plays] == [row[g] for row in want.plays], (where, "plays", g)
+        assert got.moves[g] == want.moves[g], (where, "moves", g, got.moves[g], want.moves[g])
+        assert got.states[g] == want.states[g], (where, "state", g)
+        assert len(got_examples[g]) == len(want.examples[g]), (where, "examples", g, len(got_examples[g]), len(want.examples[g]))
+        for j, (a, b) in enumerate(zip(got_examples[g], want.examples[g])):
+            assert a == b, (where, "example", g, j, a, b)
