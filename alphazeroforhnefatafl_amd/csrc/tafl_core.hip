@@ -215,13 +215,7 @@ __global__ __launch_bounds__(256) void k_encode_boards(Consts<NL> C, const Quad*
     const uint32_t aw = la == 0 ? qa.x : la == 1 ? qa.y : la == 2 ? qa.z : qa.w;
     const uint32_t dw = ld == 0 ? qd.x : ld == 1 ? qd.y : ld == 2 ? qd.z : qd.w;
     const Quad meta = soa[(size_t)(2 * NL + 4) / 4 * n_games + g];
-    const uint32_t flags = meta.w, krow = TAFL_F_KROW(flags), kcol = TAFL_F_KCOL(flags);
-    uint32_t v = 0;
-    if ((r == 0 || r == C.n - 1) && (c == 0 || c == C.n - 1)) v = 20;
-    if (r == C.n / 2 && c == C.n / 2) v = 30;
-    const bool d = (dw >> (bit & 31)) & 1u, a = (aw >> (bit & 31)) & 1u;
-    if (d) v += (r == krow && c == kcol) ? 5u : 1u; else if (a) v += 1u;
-    out[i] = (uint8_t)v;
+    out[i] = (uint8_t)board_value((aw >> (bit & 31)) & 1u, (dw >> (bit & 31)) & 1u, r, c, C.n, meta.w);
 }
 
 // ---- errors, timing spans ----------------------------------------------------------------------------

@@ -1,7 +1,10 @@
-// tafl_examples.hpp — training examples recorded by a self-play run (tafl_selfplay_record): the device-resident
-// buffer, the choice of the play (argmax or a draw in proportion to the visit counts, in integers), the result of an example and the
-// eight symmetries of the square on tiles and dense actions.  __host__ __device__ like everything in tafl_ops.hpp: the kernels run these
-// functions one game (or one example) per lane, tests/hostsim runs the same code on the CPU.
+// tafl_examples.hpp — training examples recorded by a self-play run (tafl_selfplay_record and tafl_gselfplay_*, DESIGN.md sections 12-13):
+// the device-resident buffer, the result of an example and the eight symmetries of the square on tiles and dense actions.  Two decisions
+// that both search modes and the network-input kernels share are made here and nowhere else:
+//   board_value     the board_to_matrix encoding of a tile (k_encode_boards, k_gmcts_leaves and example_append call it)
+//   example_append  the layout of a recorded example; Ops (tafl_ops.hpp) and Guided (tafl_guided.hpp) only enumerate their root children
+// and so is the draw of a play in proportion to the visit counts (visit_draw).  __host__ __device__ like everything in tafl_ops.hpp: the
+// kernels run these functions one game (or one example, or one tile) per lane, tests/hostsim runs the same code on the CPU.
 #pragma once
 #include "tafl_core.hpp"
 
@@ -36,6 +39,55 @@ struct SelfPlayRec {
     uint64_t sample_seed, game_id_base;
     uint32_t temp_moves, move_base;
 };
+
+// board_to_matrix (game/main.rs:55-83) of tile (r, c) of an n x n board: corner 20, throne 30, + 1 for a piece, + 5 for the king.  `att` /
+// `def`: the tile holds an attacker / a defender (the king is a defender); flags: the state's flags word (it names the king's tile).
+static TAFL_HD uint32_t board_value(bool att, bool def, uint32_t r, uint32_t c, uint32_t n, uint32_t flags) {
+    uint32_t v = 0;
+    if ((r == 0 || r == n - 1u) && (c == 0 || c == n - 1u)) v = 20;
+    if (r == n / 2u && c == n / 2u) v = 30;
+    if (def) v += (r == TAFL_F_KROW(flags) && c == TAFL_F_KCOL(flags)) ? 5u : 1u; else if (att) v += 1u;
+    return v;
+}
+
+// Appends the example of the move game g is about to make from `st` (W columns per row): m visited root children, `played` = dense action
+// of the play.  each(put) calls put(action, Nsa) for every visited root child in canonical order; it is called only if the children fit
+// in K (otherwise the example is marked kExOverflow and stores none).
+template <int NL, int W, class Each>
+static TAFL_HD void example_append(const ExamplesMem& X, uint32_t g, const DState<NL>& st, uint32_t n, uint32_t m, uint32_t played, uint32_t move_no, Each&& each) {
+    const uint32_t j = X.len[g];
+    if (j >= X.max_moves) { TAFL_COUNT_ADD(&X.counters[EX_DROPPED], 1); return; }
+    const size_t e = (size_t)j * X.G + g;
+    uint32_t w = 0, t = 0;
+    for (uint32_t r = 0; r < n; ++r)
+        for (uint32_t c = 0; c < n; ++c) {
+            const uint32_t bit = r * (uint32_t)W + c;
+            w |= board_value(test(st.att, bit), test(st.def, bit), r, c, n, st.flags) << (8u * (t & 3u));
+            if ((t & 3u) == 3u) { X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w; w = 0; }
+            ++t;
+        }
+    if (t & 3u) X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w;
+    const bool over = m > X.K;
+    uint32_t total = 0, k = 0;
+    if (over) TAFL_COUNT_ADD(&X.counters[EX_OVERFLOWED], 1);
+    else each([&](uint32_t a, uint32_t v) { X.pol[((size_t)j * X.K + k) * X.G + g] = a | (v << 16); total += v; ++k; });
+    X.info[e] = (over ? kExOverflow : m) | (((st.flags & TAFL_F_SIDE) ? (uint32_t)TAFL_DEFENDER : (uint32_t)TAFL_ATTACKER) << 16);
+    X.played[e] = played | (total << 16); X.move_no[e] = move_no; X.z[e] = 0.0f; X.fin[e] = 0;
+    X.len[g] = j + 1u;
+}
+
+// The entry a move is drawn with, among n entries of which entry j has count(j) visits: k = mulhi(r, N) = (r * N) >> 32 with N = the sum of
+// the counts, and the draw is the first entry in canonical (= ascending action) order whose running sum exceeds k: entry j is drawn for
+// floor-exact count(j) / N of the 2^32 values of r.  Integers only.  Entries without visits (the unvisited edges of a guided root) add
+// nothing to the running sum, so skipping them cannot change which entry passes first.  Both callers (Ops::selfplay_pick, Guided::selfplay_pick) pass N = the sum of the counts with
+// N > 0; then k < N and the running sum always passes it, so the fallback (the last visited entry) is never reached.
+template <class Count>
+static TAFL_HD uint32_t visit_draw(uint32_t n, uint32_t N, uint32_t r, Count&& count) {
+    const uint32_t k = Engine<2, 7>::mulhi(r, N);
+    uint32_t run = 0, last = 0;
+    for (uint32_t j = 0; j < n; ++j) { const uint32_t v = count(j); if (v == 0) continue; run += v; last = j; if (run > k) return j; }
+    return last;
+}
 
 // ---- the eight symmetries of the square -----------------------------------------------------------------------------------------
 // bit 2 of sym transposes (r, c) -> (c, r) first, then bit 0 mirrors the rows r -> n-1-r, then bit 1 mirrors the columns c -> n-1-c.

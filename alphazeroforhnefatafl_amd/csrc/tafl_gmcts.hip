@@ -2,6 +2,15 @@
 #include "tafl_internal.hpp"
 
 enum { GS_SIMS = 0, GS_PREDICTS, GS_TERMINAL, GS_FAULTS, GS_DEPTH, GS_WAITING, GS_COUNT };
+// what one lane's round adds to the counters of a step kernel
+static __device__ __forceinline__ void gstats_flush(const GuidedStats& gs, bool waiting, unsigned long long* stats) {
+    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
+    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
+    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
+    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
+    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
+    if (waiting) atomicAdd(&stats[GS_WAITING], 1ull);
+}
 
 template <int NL, int W>
 __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_init(Consts<NL> C, const Quad* soa, GuidedMem M) {
@@ -17,12 +26,7 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_step(Consts<NL> C, GuidedM
     if (g >= M.G) return;
     GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
     Guided<NL, W>::step(M, g, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, C, gs);
-    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
-    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
-    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
-    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
-    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
-    if (M.kind[g] == 1) atomicAdd(&stats[GS_WAITING], 1ull);
+    gstats_flush(gs, M.kind[g] == 1, stats);
 }
 // network input of the waiting leaves: board_to_matrix planes (game/main.rs:55-83), side to move, waiting flag; one thread per tile
 template <int NL, int W>
@@ -35,12 +39,7 @@ __global__ __launch_bounds__(256) void k_gmcts_leaves(Consts<NL> C, GuidedMem M,
     const uint32_t L = wait ? M.leaf[g] : 0u;
     const uint32_t* rec = (const uint32_t*)(M.node_state + ((size_t)L * M.G + g) * StateIO<NL>::QUADS);   // att[NL], def[NL], rep[4], meta[4]
     const uint32_t aw = rec[bit >> 5], dw = rec[NL + (bit >> 5)], flags = rec[2 * NL + 7];
-    uint32_t v = 0;
-    if ((r == 0 || r == C.n - 1) && (c == 0 || c == C.n - 1)) v = 20;
-    if (r == C.n / 2 && c == C.n / 2) v = 30;
-    const bool d = (dw >> (bit & 31)) & 1u, a = (aw >> (bit & 31)) & 1u;
-    if (d) v += (r == TAFL_F_KROW(flags) && c == TAFL_F_KCOL(flags)) ? 5u : 1u; else if (a) v += 1u;
-    boards[i] = (uint8_t)v;
+    boards[i] = (uint8_t)board_value((aw >> (bit & 31)) & 1u, (dw >> (bit & 31)) & 1u, r, c, C.n, flags);
     if (t == 0) { sides[g] = (uint8_t)((flags & TAFL_F_SIDE) ? TAFL_DEFENDER : TAFL_ATTACKER); waiting[g] = wait ? 1 : 0; }
 }
 template <int NL, int W>
@@ -138,12 +137,7 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_step(Consts<NL> C, Gui
     if (g >= M.G) return;
     GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
     Guided<NL, W>::selfplay_step(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, rec, C, gs);
-    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
-    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
-    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
-    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
-    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
-    if (M.kind[g] == 1) atomicAdd(&stats[GS_WAITING], 1ull);
+    gstats_flush(gs, M.kind[g] == 1, stats);
 }
 
 // the arena of a search from fresh roots: max_sims + 1 nodes and (max_sims + 1) x edges_per_node edges per game; the guided stats are zeroed
@@ -161,6 +155,16 @@ static int gmcts_arena(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node
     b->g_node_top.bind(M.node_top); b->g_edge_top.bind(M.edge_top); b->g_leaf.bind(M.leaf); b->g_kind.bind(M.kind);
     b->g_fault.bind(M.fault); b->g_sims.bind(M.sims_done); M.G = n; M.node_cap = node_cap; M.edge_cap = (uint32_t)ecap;
     HIPCHK(hipMemsetAsync(b->g_stats.p, 0, sizeof(unsigned long long) * GS_COUNT, c->stream));
+    return TAFL_OK;
+}
+// the evaluator's answer where the step kernels read it: host arrays are copied to g_priors / g_values, device pointers (and none) pass through
+static int stage_evaluation(tafl_batch* b, const float*& priors, const float*& values, int in_is_device) {
+    if (!priors || in_is_device) return TAFL_OK;
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    NEED(b->g_priors, sizeof(float) * (size_t)n * A); NEED(b->g_values, sizeof(float) * (size_t)n);
+    HIPCHK(hipMemcpyAsync(b->g_priors.p, priors, sizeof(float) * (size_t)n * A, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(b->g_values.p, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    priors = b->g_priors.as<const float>(); values = b->g_values.as<const float>();
     return TAFL_OK;
 }
 // the games now waiting for predict(), as the last step kernel counted them
@@ -226,16 +230,10 @@ int tafl_gmcts_step(tafl_batch* b, const float* priors, const float* values, int
     if ((priors == nullptr) != (values == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_step: priors and values go together");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     HIPCHK(hipSetDevice(c->device));
-    const float* dp = priors; const float* dv = values;
-    if (priors && !in_is_device) {
-        NEED(b->g_priors, sizeof(float) * (size_t)n * A); NEED(b->g_values, sizeof(float) * (size_t)n);
-        HIPCHK(hipMemcpyAsync(b->g_priors.p, priors, sizeof(float) * (size_t)n * A, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(b->g_values.p, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        dp = b->g_priors.as<const float>(); dv = b->g_values.as<const float>();
-    }
+    if (const int rc = stage_evaluation(b, priors, values, in_is_device)) return rc;
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, dp, dv, A, c_puct, n_sims, st); });
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st); });
     HIPCHK(hipGetLastError());
     return gmcts_waiting(b, out_waiting);
 }
@@ -383,17 +381,10 @@ int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values,
     if (!b || !b->gsp_active) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: no run is open on this batch (tafl_gselfplay_begin first; a write to the batch states closes a run)");
     if ((priors == nullptr) != (values == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: priors and values go together");
     if (b->gsp_first != (priors == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: the first step after tafl_gselfplay_begin, and only that one, takes priors = values = NULL");
-    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
-    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipSetDevice(b->ctx->device));
     if (b->gsp_first) { b->gsp_first = false; return gmcts_waiting(b, out_waiting); }      // (tafl_gselfplay_begin ran that round)
-    const float* dp = priors; const float* dv = values;
-    if (!in_is_device) {
-        NEED(b->g_priors, sizeof(float) * (size_t)n * A); NEED(b->g_values, sizeof(float) * (size_t)n);
-        HIPCHK(hipMemcpyAsync(b->g_priors.p, priors, sizeof(float) * (size_t)n * A, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(hipMemcpyAsync(b->g_values.p, values, sizeof(float) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        dp = b->g_priors.as<const float>(); dv = b->g_values.as<const float>();
-    }
-    if (const int rc = gselfplay_launch(b, dp, dv)) return rc;
+    if (const int rc = stage_evaluation(b, priors, values, in_is_device)) return rc;
+    if (const int rc = gselfplay_launch(b, priors, values)) return rc;
     return gmcts_waiting(b, out_waiting);
 }
 

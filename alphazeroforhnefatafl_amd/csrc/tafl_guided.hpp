@@ -15,6 +15,9 @@
 //
 // Storage differs from the rollout mode (tafl_ops.hpp): with non-uniform priors the visited children are no longer a prefix
 // of the legal list, so a node owns one edge per LEGAL move, in canonical (= ascending action index) order.
+//
+// A guided self-play run records its examples and draws its plays with the functions of tafl_examples.hpp (example_append,
+// visit_draw, which own the example layout and the board encoding); this file only walks the root's edge block for them.
 #pragma once
 #include "tafl_ops.hpp"
 
@@ -290,42 +293,8 @@ struct Guided {
     }
 
     // ---- guided self-play at each game's own pace (tafl_gselfplay_*) -----------------------------------------
-    // Ops::selfplay_pick over the root's edge block: k = mulhi(r, N) with N = sum of Nsa, and the play is the first edge in ascending action
-    // order whose running sum of Nsa exceeds k.  The block holds one edge per LEGAL move, so unvisited edges (n == 0) lie between the
-    // visited ones; they add nothing to the running sum and are never drawn.  Returns the index inside the block.  Integers only.
-    static TAFL_HD uint32_t selfplay_pick(const GEdge* eb, uint32_t n_legal, uint32_t N, uint32_t r) {
-        const uint32_t k = E::mulhi(r, N);
-        uint32_t run = 0, last = 0;
-        for (uint32_t j = 0; j < n_legal; ++j) { const uint32_t v = eb[j].n; if (v == 0) continue; run += v; last = j; if (run > k) return j; }
-        return last;
-    }
-    // Ops::example_record over the root's edge block: appends the example of the move game g is about to make from `st` (m visited edges,
-    // play = edge `pick`).  The action is in the edge: no child header is read.
-    static TAFL_HD void example_record(uint32_t g, const ExamplesMem& X, const S& st, const GEdge* eb, uint32_t n_legal, uint32_t m, uint32_t pick, uint32_t move_no, const K& C) {
-        const uint32_t j = X.len[g];
-        if (j >= X.max_moves) { TAFL_COUNT_ADD(&X.counters[EX_DROPPED], 1); return; }
-        const size_t e = (size_t)j * X.G + g;
-        uint32_t w = 0, t = 0;
-        for (uint32_t r = 0; r < C.n; ++r)
-            for (uint32_t c = 0; c < C.n; ++c) {
-                w |= O::board_byte(st, r, c, C) << (8u * (t & 3u));
-                if ((t & 3u) == 3u) { X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w; w = 0; }
-                ++t;
-            }
-        if (t & 3u) X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w;
-        const bool over = m > X.K;
-        uint32_t total = 0;
-        if (!over)
-            for (uint32_t i = 0, k = 0; i < n_legal; ++i) {
-                const uint32_t v = eb[i].n;
-                if (v == 0) continue;
-                X.pol[((size_t)j * X.K + k) * X.G + g] = eb[i].action | (v << 16); total += v; ++k;
-            }
-        if (over) TAFL_COUNT_ADD(&X.counters[EX_OVERFLOWED], 1);
-        X.info[e] = (over ? kExOverflow : m) | (((st.flags & TAFL_F_SIDE) ? (uint32_t)TAFL_DEFENDER : (uint32_t)TAFL_ATTACKER) << 16);
-        X.played[e] = eb[pick].action | (total << 16); X.move_no[e] = move_no; X.z[e] = 0.0f; X.fin[e] = 0;
-        X.len[g] = j + 1u;
-    }
+    // visit_draw (tafl_examples.hpp) over the root's edge block (one edge per LEGAL move, the unvisited ones in between): the index inside the block
+    static TAFL_HD uint32_t selfplay_pick(const GEdge* eb, uint32_t n_legal, uint32_t N, uint32_t r) { return visit_draw(n_legal, N, r, [&](uint32_t j) { return eb[j].n; }); }
     // the start of a run for game g: a fresh root from its batch state; a game that is over makes no move
     static TAFL_HD void selfplay_init(const GuidedMem& M, uint32_t g, const S& root, const GSelfPlay& sp) {
         init_game(M, g, root);
@@ -361,7 +330,12 @@ struct Guided {
             if (move_no < rec.temp_moves) pick = selfplay_pick(eb, h.n_legal, total, selfplay_rand(rec.sample_seed, rec.game_id_base + g, move_no));
             const GEdge pe = eb[pick];
             S st;
-            if (rec.ex.len) { IO::load_soa(soa, M.G, g, st); example_record(g, rec.ex, st, eb, h.n_legal, m, pick, move_no, C); }
+            if (rec.ex.len) {                                                // (tafl_examples.hpp; a guided edge carries its action, unvisited edges lie in between)
+                IO::load_soa(soa, M.G, g, st);
+                example_append<NL, W>(rec.ex, g, st, C.n, m, pe.action, move_no, [&](auto&& put) {
+                    for (uint32_t i = 0; i < h.n_legal; ++i) if (eb[i].n != 0u) put(eb[i].action, eb[i].n);
+                });
+            }
             IO::load_rec(M.node_state + ((size_t)pe.child * M.G + g) * IO::QUADS, st);
             IO::store_soa(soa, M.G, g, st);
             Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;

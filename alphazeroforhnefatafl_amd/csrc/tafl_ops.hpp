@@ -5,6 +5,9 @@
 // MCTS: the arithmetic of src/mcts.py:55-136 (select :104-123, expand :83-102, backup :127-136)
 // on an explicit per-game tree (src/mcts.rs:9-28), iterative instead of recursive.  Data layout
 // in DESIGN.md "MCTS arena".
+//
+// The board_to_matrix encoding, the layout of a recorded example and the visit-proportional draw belong to tafl_examples.hpp
+// (board_value, example_append, visit_draw): the recording run here only enumerates its visited root children for them.
 #pragma once
 #include <math.h>
 #include "tafl_core.hpp"
@@ -970,52 +973,11 @@ struct Ops {
     static TAFL_HD int selfplay_advance_rec(const MctsMem& M, uint32_t g, Quad* soa, const SelfPlay& sp, const SelfPlayRec& rec, uint32_t n_sims, uint32_t round, const K& C) {
         return selfplay_advance_impl<NLS, WS, true>(M, g, soa, sp, rec, n_sims, round, C);
     }
-    // The child a move is drawn with: k = mulhi(r, N) = (r * N) >> 32 with N = sum of Nsa over the m visited root edges (N > 0), and the play is
-    // the first child in canonical (= ascending action) order whose running sum of Nsa exceeds k: child j is drawn for floor-exact
-    // Nsa_j / N of the 2^32 values of r.  Integers only.
-    static TAFL_HD uint32_t selfplay_pick(const Edge* eb, uint32_t m, uint32_t N, uint32_t r) {
-        const uint32_t k = E::mulhi(r, N);
-        uint32_t run = 0;
-        for (uint32_t j = 0; j < m; ++j) { run += eb[j].n; if (run > k) return j; }
-        return m ? m - 1u : 0u;
-    }
-    // board_to_matrix (game/main.rs:55-83, k_encode_boards) of tile (r, c)
+    // visit_draw (tafl_examples.hpp) over the m visited root edges, and board_value of tile (r, c) of a state: the bit tests in front, no rule here
+    static TAFL_HD uint32_t selfplay_pick(const Edge* eb, uint32_t m, uint32_t N, uint32_t r) { return visit_draw(m, N, r, [&](uint32_t j) { return eb[j].n; }); }
     static TAFL_HD uint32_t board_byte(const S& st, uint32_t r, uint32_t c, const K& C) {
         const uint32_t bit = r * (uint32_t)W + c;
-        uint32_t v = 0;
-        if ((r == 0 || r == C.n - 1u) && (c == 0 || c == C.n - 1u)) v = 20;
-        if (r == C.n / 2u && c == C.n / 2u) v = 30;
-        if (test(st.def, bit)) v += (r == TAFL_F_KROW(st.flags) && c == TAFL_F_KCOL(st.flags)) ? 5u : 1u; else if (test(st.att, bit)) v += 1u;
-        return v;
-    }
-    // appends the example of the move game g is about to make from `st` (root header h, edges eb, play = edge `pick`)
-    static TAFL_HD void example_record(const MctsMem& M, uint32_t g, const ExamplesMem& X, const S& st, const NodeHdr& h, const Edge* eb, uint32_t pick, uint32_t move_no, const K& C) {
-        const uint32_t j = X.len[g];
-        if (j >= X.max_moves) { TAFL_COUNT_ADD(&X.counters[EX_DROPPED], 1); return; }
-        const size_t e = (size_t)j * X.G + g;
-        uint32_t w = 0, t = 0;
-        for (uint32_t r = 0; r < C.n; ++r)
-            for (uint32_t c = 0; c < C.n; ++c) {
-                w |= board_byte(st, r, c, C) << (8u * (t & 3u));
-                if ((t & 3u) == 3u) { X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w; w = 0; }
-                ++t;
-            }
-        if (t & 3u) X.boards[((size_t)j * X.BW + (t >> 2)) * X.G + g] = w;
-        const bool over = h.m > X.K;
-        uint32_t played = 0, total = 0;
-        for (uint32_t k = 0; k < h.m; ++k) {
-            if (over && k != pick) continue;
-            const Edge ed = eb[k];
-            const NodeHdr ch = M.hdr[(size_t)ed.child * M.G + g];
-            Move mv; mv.from = ch.mv_from; mv.dir = ch.mv_dir; mv.dist = ch.mv_dist; mv.to = 0;
-            const uint32_t a = action_of(mv, C);
-            if (k == pick) played = a;
-            if (!over) { X.pol[((size_t)j * X.K + k) * X.G + g] = a | (ed.n << 16); total += ed.n; }
-        }
-        if (over) TAFL_COUNT_ADD(&X.counters[EX_OVERFLOWED], 1);
-        X.info[e] = (over ? kExOverflow : (uint32_t)h.m) | (((st.flags & TAFL_F_SIDE) ? (uint32_t)TAFL_DEFENDER : (uint32_t)TAFL_ATTACKER) << 16);
-        X.played[e] = played | (total << 16); X.move_no[e] = move_no; X.z[e] = 0.0f; X.fin[e] = 0;
-        X.len[g] = j + 1u;
+        return board_value(test(st.att, bit), test(st.def, bit), r, c, C.n, st.flags);
     }
     template <int NLS, int WS, bool REC>
     static TAFL_HD int selfplay_advance_impl(const MctsMem& M, uint32_t g, Quad* soa, const SelfPlay& sp, const SelfPlayRec& rec, uint32_t n_sims, uint32_t round, const K& C) {
@@ -1025,10 +987,10 @@ struct Ops {
         const NodeHdr h = M.hdr[g];
         const Edge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
         uint32_t best = 0, child = 0;
-        [[maybe_unused]] uint32_t pick = 0, total = 0;
+        [[maybe_unused]] uint32_t total = 0;
         for (uint32_t j = 0; j < h.m; ++j) {
             const Edge e = eb[j];
-            if (e.n > best) { best = e.n; child = e.child; if constexpr (REC) pick = j; }
+            if (e.n > best) { best = e.n; child = e.child; }
             if constexpr (REC) total += e.n;
         }
         S st;
@@ -1036,14 +998,26 @@ struct Ops {
         else { DState<NLS> t; StateIO<NLS>::load_soa(soa, M.G, g, t); restride<NLS, WS, NL, W>(t, C.n, st); }
         tafl_play p; p.from_row = p.from_col = p.axis = 0; p.disp = 0;
         if (best > 0 && TAFL_F_STATUS(st.flags) == TAFL_STATUS_ONGOING) {
+            [[maybe_unused]] uint32_t move_no = 0;
             if constexpr (REC) {
-                const uint32_t move_no = rec.move_base + md;
-                if (move_no < rec.temp_moves) { pick = selfplay_pick(eb, h.m, total, selfplay_rand(rec.sample_seed, rec.game_id_base + g, move_no)); child = eb[pick].child; }
-                if (rec.ex.len) example_record(M, g, rec.ex, st, h, eb, pick, move_no, C);
+                move_no = rec.move_base + md;
+                if (move_no < rec.temp_moves)
+                    child = eb[selfplay_pick(eb, h.m, total, selfplay_rand(rec.sample_seed, rec.game_id_base + g, move_no))].child;
             }
             const NodeHdr ch = M.hdr[(size_t)child * M.G + g];
             Move bm; bm.from = ch.mv_from; bm.dir = ch.mv_dir; bm.dist = ch.mv_dist;
             bm.to = (uint32_t)((int)bm.from + E::delta(bm.dir) * (int)bm.dist);
+            // the example of the move (tafl_examples.hpp): a visited child's action is in the child's header
+            if constexpr (REC)
+                if (rec.ex.len)
+                    example_append<NL, W>(rec.ex, g, st, C.n, h.m, action_of(bm, C), move_no, [&](auto&& put) {
+                        for (uint32_t k = 0; k < h.m; ++k) {
+                            const Edge ed = eb[k];
+                            const NodeHdr kh = M.hdr[(size_t)ed.child * M.G + g];
+                            Move mv; mv.from = kh.mv_from; mv.dir = kh.mv_dir; mv.dist = kh.mv_dist; mv.to = 0;
+                            put(action_of(mv, C), ed.n);
+                        }
+                    });
             p = to_play(bm);
             Moves<NL> nx;
             E::apply(st, bm, C, nullptr, nx);

@@ -1,15 +1,14 @@
 """Expected values for the training-example tests (include/taflhip.h tafl_selfplay_record), from the oracle and
-from Python restatements of the build-defined rules - never from the code under test - and the loader of the host harness
-tests/hostsim_examples/libhostsim_examples.so (the product's per-game functions compiled for the CPU)."""
+from Python restatements of the build-defined rules - never from the code under test - and the front end of the host harness's
+recording run (tests/hostsim, hsx_*: the product's per-game functions compiled for the CPU)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from alphazeroforhnefatafl_amd import abi
-from alphazeroforhnefatafl_amd.abi import TaflMctsParams, TaflMctsStats, TaflPlay, TaflRules, TaflSelfplayOpts, TaflState
+from alphazeroforhnefatafl_amd.abi import TaflMctsParams, TaflMctsStats, TaflPlay, TaflSelfplayOpts, TaflState
 from tests import parity_util as pu
+from tests.hostsim import hostsim
 
 M32 = 0xFFFFFFFF
 DRAW_Z = np.float32(1e-4)
@@ -183,47 +182,16 @@ def dense_pi(n, e: Example, k=0):
 
 
 # ---- the host harness ---------------------------------------------------------------------------------------------------------
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_examples")
-_LIB = None
+hlib = hostsim.lib
 
 
-def hlib():
-    global _LIB
-    if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s", "libhostsim_examples.so"])
-        L = C.CDLL(os.path.join(_HERE, "libhostsim_examples.so"))
-        P, u8, u32, u64, vp = C.POINTER, C.c_uint8, C.c_uint32, C.c_uint64, C.c_void_p
-        L.hsx_new.restype = vp; L.hsx_new.argtypes = [u32, u8, u32, u32]
-        L.hsx_free.restype = None; L.hsx_free.argtypes = [vp]
-        L.hsx_clear.restype = None; L.hsx_clear.argtypes = [vp]
-        L.hsx_counts.restype = None; L.hsx_counts.argtypes = [vp, P(u32), P(u64)]
-        L.hsx_example.restype = C.c_int; L.hsx_example.argtypes = [vp, u32, P(u32), P(u8), P(u32), P(u32), P(C.c_float), P(u8)]
-        L.hsx_record.restype = C.c_int
-        L.hsx_record.argtypes = [P(TaflRules), u8, u32, P(TaflState), u32, P(TaflMctsParams), u64, u32, P(TaflSelfplayOpts), vp, P(TaflPlay),
-                                 P(TaflMctsStats), u32, u32, u32]
-        L.hsx_finalize.restype = C.c_int; L.hsx_finalize.argtypes = [vp, u8, u32, P(TaflState)]
-        L.hsx_gather.restype = u32; L.hsx_gather.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
-        L.hsx_pick.restype = u32; L.hsx_pick.argtypes = [P(u32), u32, u32]
-        L.hsx_pick_many.restype = None; L.hsx_pick_many.argtypes = [P(u32), u32, P(u32), u32, P(u32)]
-        L.hsx_rand.restype = u32; L.hsx_rand.argtypes = [u64, u64, u32]
-        L.hsx_sym_tables.restype = None; L.hsx_sym_tables.argtypes = [u32, u32, P(u32), P(u32)]
-        L.hsx_set_dense13.restype = None; L.hsx_set_dense13.argtypes = [C.c_int]
-        _LIB = L
-    return _LIB
-
-
-class HostExamples:
+class HostExamples(hostsim.HostExamples):
     """tafl_examples on host memory + the recording run, finalize and gather of the harness."""
 
     def __init__(self, rules, n, wb, G, max_moves, K):
         self.rules = rules.to_c() if isinstance(rules, abi.Ruleset) else rules
-        self.n, self.wb, self.G, self.max_moves, self.K = n, wb, G, max_moves, K
-        self.h = hlib().hsx_new(G, n, max_moves, K)
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            hlib().hsx_free(self.h)
-            self.h = None
+        self.wb = wb
+        super().__init__(n, G, max_moves, K)
 
     def record(self, states, params, n_moves, base, sample_seed, temp_moves, move_base=0, spec=(4, 0, 0), record=True):
         plays, stats = (TaflPlay * (self.G * n_moves))(), TaflMctsStats()
@@ -236,19 +204,11 @@ class HostExamples:
     def finalize(self, states):
         assert hlib().hsx_finalize(self.h, self.n, self.wb, states) == 0
 
-    def counts(self):
-        ln, ct = (C.c_uint32 * self.G)(), (C.c_uint64 * 4)()
-        hlib().hsx_counts(self.h, ln, ct)
-        return list(ln), {"dropped": ct[0], "overflowed": ct[1], "bad_index": ct[2]}
-
     def example(self, j, g):
         """Example (j, g) as the tuple Example.fields() gives + (overflow, z, final)."""
-        out5, board = (C.c_uint32 * 5)(), (C.c_uint8 * (self.n * self.n))()
-        acts, vis, z, fin = (C.c_uint32 * self.K)(), (C.c_uint32 * self.K)(), C.c_float(), C.c_uint8()
-        assert hlib().hsx_example(self.h, j * self.G + g, out5, board, acts, vis, C.byref(z), C.byref(fin)) == 0, (j, g)
-        k = out5[0]
-        rows = [list(board[r * self.n:(r + 1) * self.n]) for r in range(self.n)]
-        return (rows, out5[1], list(acts[:k]), list(vis[:k]), out5[3], out5[4]), out5[2], np.float32(z.value), fin.value
+        z, fin = C.c_float(), C.c_uint8()
+        fields, overflow = self._example(j, g, C.byref(z), C.byref(fin))
+        return fields, overflow, np.float32(z.value), fin.value
 
     def gather(self, index, sym=None):
         idx = np.ascontiguousarray(index, np.uint32)

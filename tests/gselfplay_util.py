@@ -1,16 +1,15 @@
 """Expected values and drivers for the guided self-play tests (include/taflhip.h tafl_gselfplay_*): the oracle loop
 - orc.GameLogic.gmcts, the pick rule and the RNG word restated in tests/examples_util.py, the oracle's do_play - and the loader of the
-host harness tests/hostsim_gselfplay/libhostsim_gselfplay.so (Guided::selfplay_step compiled for the CPU)."""
+host harness's guided run (tests/hostsim, hsg_*: Guided::selfplay_step compiled for the CPU)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from alphazeroforhnefatafl_amd import abi
-from alphazeroforhnefatafl_amd.abi import TaflPlay, TaflRules, TaflSelfplayOpts, TaflState
+from alphazeroforhnefatafl_amd.abi import TaflPlay, TaflSelfplayOpts, TaflState
 from tests import examples_util as eu
 from tests import parity_util as pu
+from tests.hostsim import hostsim
 from tests.stub_net import matrix_bytes_of, stub_predict
 
 _STUB = {}
@@ -87,57 +86,15 @@ def oracle_run(orc, lg, states, wb, S, c_puct, salts, n_moves, sample_seed, temp
 
 
 # ---- the host harness ---------------------------------------------------------------------------------------------------------
-_HERE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "hostsim_gselfplay")
-_LIB = None
+hlib = hostsim.lib
 
 
-def hlib():
-    global _LIB
-    if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s", "libhostsim_gselfplay.so"])
-        L = C.CDLL(os.path.join(_HERE, "libhostsim_gselfplay.so"))
-        P, u8, u32, u64, vp = C.POINTER, C.c_uint8, C.c_uint32, C.c_uint64, C.c_void_p
-        L.hsg_ex_new.restype = vp; L.hsg_ex_new.argtypes = [u32, u8, u32, u32]
-        L.hsg_ex_free.restype = None; L.hsg_ex_free.argtypes = [vp]
-        L.hsg_ex_counts.restype = None; L.hsg_ex_counts.argtypes = [vp, P(u32), P(u64)]
-        L.hsg_ex_example.restype = C.c_int; L.hsg_ex_example.argtypes = [vp, u32, P(u32), P(u8), P(u32), P(u32)]
-        L.hsg_begin.restype = vp
-        L.hsg_begin.argtypes = [P(TaflRules), u8, u32, P(TaflState), u32, u32, u32, C.c_double, P(TaflSelfplayOpts), u32, u64, vp]
-        L.hsg_free.restype = None; L.hsg_free.argtypes = [vp]
-        L.hsg_step.restype = u32; L.hsg_step.argtypes = [vp, P(C.c_float), P(C.c_float)]
-        L.hsg_leaves.restype = None; L.hsg_leaves.argtypes = [vp, P(u8), P(u8), P(u8)]
-        L.hsg_end.restype = None; L.hsg_end.argtypes = [vp, P(TaflState), P(TaflPlay), P(u32), P(u64), P(u8)]
-        L.hsg_pick_many.restype = None; L.hsg_pick_many.argtypes = [P(u32), u32, P(u32), u32, P(u32)]
-        L.hsg_rand.restype = u32; L.hsg_rand.argtypes = [u64, u64, u32]
-        _LIB = L
-    return _LIB
-
-
-class HostExamples:
-    """tafl_examples on host memory."""
-
-    def __init__(self, n, G, max_moves, K):
-        self.n, self.G, self.max_moves, self.K = n, G, max_moves, K
-        self.h = hlib().hsg_ex_new(G, n, max_moves, K)
-
-    def __del__(self):
-        if getattr(self, "h", None):
-            hlib().hsg_ex_free(self.h)
-            self.h = None
-
-    def counts(self):
-        ln, ct = (C.c_uint32 * self.G)(), (C.c_uint64 * 4)()
-        hlib().hsg_ex_counts(self.h, ln, ct)
-        return list(ln), {"dropped": ct[0], "overflowed": ct[1], "bad_index": ct[2]}
+class HostExamples(hostsim.HostExamples):
+    pre = "hsg_ex_"
 
     def example(self, j, g):
         """(Example.fields() tuple, overflow) of example (j, g)."""
-        out5, board = (C.c_uint32 * 5)(), (C.c_uint8 * (self.n * self.n))()
-        acts, vis = (C.c_uint32 * self.K)(), (C.c_uint32 * self.K)()
-        assert hlib().hsg_ex_example(self.h, j * self.G + g, out5, board, acts, vis) == 0, (j, g)
-        k = out5[0]
-        rows = [list(board[r * self.n:(r + 1) * self.n]) for r in range(self.n)]
-        return (rows, out5[1], list(acts[:k]), list(vis[:k]), out5[3], out5[4]), out5[2]
+        return self._example(j, g)
 
     def all(self):
         """(examples per game as fields tuples, overflow marks per game)."""

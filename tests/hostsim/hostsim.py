@@ -5,7 +5,7 @@ import subprocess
 
 from alphazeroforhnefatafl_amd import abi
 from alphazeroforhnefatafl_amd.abi import (TaflEffects, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult,
-                                          TaflRootChild, TaflRules, TaflState)
+                                          TaflRootChild, TaflRules, TaflSelfplayOpts, TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
@@ -14,7 +14,7 @@ _LIB = None
 def lib():
     global _LIB
     if _LIB is None:
-        subprocess.check_call(["make", "-C", _HERE, "-s", "libhostsim.so"])
+        subprocess.check_call(["make", "-C", _HERE, "-s"])
         L = C.CDLL(os.path.join(_HERE, "libhostsim.so"))
         P, u8, u32, u64, i32 = C.POINTER, C.c_uint8, C.c_uint32, C.c_uint64, C.c_int
         head = [P(TaflRules), u8, u32]
@@ -64,6 +64,35 @@ def lib():
         L.hs_set_spec_k.argtypes = [C.c_uint32]
         L.hs_force_generic.restype = None
         L.hs_force_generic.argtypes = [C.c_int]
+        # the examples buffer on host memory, the recording run, results and gather (hsx_*, hostsim_examples.cpp)
+        L.hsx_new.restype = vp; L.hsx_new.argtypes = [u32, u8, u32, u32]
+        L.hsx_free.restype = None; L.hsx_free.argtypes = [vp]
+        L.hsx_clear.restype = None; L.hsx_clear.argtypes = [vp]
+        L.hsx_counts.restype = None; L.hsx_counts.argtypes = [vp, P(u32), P(u64)]
+        L.hsx_example.restype = i32; L.hsx_example.argtypes = [vp, u32, P(u32), P(u8), P(u32), P(u32), P(C.c_float), P(u8)]
+        L.hsx_record.restype = i32
+        L.hsx_record.argtypes = [P(TaflRules), u8, u32, P(TaflState), u32, P(TaflMctsParams), u64, u32, P(TaflSelfplayOpts), vp, P(TaflPlay),
+                                 P(TaflMctsStats), u32, u32, u32]
+        L.hsx_finalize.restype = i32; L.hsx_finalize.argtypes = [vp, u8, u32, P(TaflState)]
+        L.hsx_gather.restype = u32; L.hsx_gather.argtypes = [vp, vp, vp, u32, vp, vp, vp, vp, vp]
+        L.hsx_pick.restype = u32; L.hsx_pick.argtypes = [P(u32), u32, u32]
+        L.hsx_pick_many.restype = None; L.hsx_pick_many.argtypes = [P(u32), u32, P(u32), u32, P(u32)]
+        L.hsx_rand.restype = u32; L.hsx_rand.argtypes = [u64, u64, u32]
+        L.hsx_sym_tables.restype = None; L.hsx_sym_tables.argtypes = [u32, u32, P(u32), P(u32)]
+        L.hsx_set_dense13.restype = None; L.hsx_set_dense13.argtypes = [i32]
+        # the guided self-play run (hsg_*, hostsim_gselfplay.cpp)
+        L.hsg_ex_new.restype = vp; L.hsg_ex_new.argtypes = [u32, u8, u32, u32]
+        L.hsg_ex_free.restype = None; L.hsg_ex_free.argtypes = [vp]
+        L.hsg_ex_counts.restype = None; L.hsg_ex_counts.argtypes = [vp, P(u32), P(u64)]
+        L.hsg_ex_example.restype = i32; L.hsg_ex_example.argtypes = [vp, u32, P(u32), P(u8), P(u32), P(u32)]
+        L.hsg_begin.restype = vp
+        L.hsg_begin.argtypes = [P(TaflRules), u8, u32, P(TaflState), u32, u32, u32, C.c_double, P(TaflSelfplayOpts), u32, u64, vp]
+        L.hsg_free.restype = None; L.hsg_free.argtypes = [vp]
+        L.hsg_step.restype = u32; L.hsg_step.argtypes = [vp, P(C.c_float), P(C.c_float)]
+        L.hsg_leaves.restype = None; L.hsg_leaves.argtypes = [vp, P(u8), P(u8), P(u8)]
+        L.hsg_end.restype = None; L.hsg_end.argtypes = [vp, P(TaflState), P(TaflPlay), P(u32), P(u64), P(u8)]
+        L.hsg_pick_many.restype = None; L.hsg_pick_many.argtypes = [P(u32), u32, P(u32), u32, P(u32)]
+        L.hsg_rand.restype = u32; L.hsg_rand.argtypes = [u64, u64, u32]
         _LIB = L
     return _LIB
 
@@ -163,3 +192,31 @@ def round_work():
 def set_dense13(on: bool):
     """Rollouts / searches of 13x13 positions in the dense 13-column layout (what the library does for the 13x13 preset)."""
     lib().hs_set_dense13(int(on))
+
+
+class HostExamples:
+    """tafl_examples on host memory.  `pre`: the family of entry points the buffer is used with ("hsx_" rollout mode, "hsg_ex_" guided)."""
+    pre = "hsx_"
+
+    def __init__(self, n, G, max_moves, K):
+        self.n, self.G, self.max_moves, self.K = n, G, max_moves, K
+        self.h = getattr(lib(), self.pre + "new")(G, n, max_moves, K)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            getattr(lib(), self.pre + "free")(self.h)
+            self.h = None
+
+    def counts(self):
+        ln, ct = (C.c_uint32 * self.G)(), (C.c_uint64 * 4)()
+        getattr(lib(), self.pre + "counts")(self.h, ln, ct)
+        return list(ln), {"dropped": ct[0], "overflowed": ct[1], "bad_index": ct[2]}
+
+    def _example(self, j, g, *more):
+        """(Example.fields() tuple, overflow) of example (j, g); `more`: further outputs of the family's reader."""
+        out5, board = (C.c_uint32 * 5)(), (C.c_uint8 * (self.n * self.n))()
+        acts, vis = (C.c_uint32 * self.K)(), (C.c_uint32 * self.K)()
+        assert getattr(lib(), self.pre + "example")(self.h, j * self.G + g, out5, board, acts, vis, *more) == 0, (j, g)
+        k = out5[0]
+        rows = [list(board[r * self.n:(r + 1) * self.n]) for r in range(self.n)]
+        return (rows, out5[1], list(acts[:k]), list(vis[:k]), out5[3], out5[4]), out5[2]

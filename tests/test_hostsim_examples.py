@@ -1,6 +1,6 @@
 """Training examples of a recording self-play run (include/taflhip.h tafl_selfplay_record), CPU only: the product's
 per-game functions (selfplay_pick, selfplay_advance_rec, example_outcome, sym_tile, sym_action) compiled for the host
-(tests/hostsim_examples/hostsim_examples.cpp) against the oracle loop and the Python restatements of tests/examples_util.py.  The same
+(tests/hostsim/hostsim_examples.cpp) against the oracle loop and the Python restatements of tests/examples_util.py.  The same
 comparisons run against the real kernels in tests/test_gpu_examples.py."""
 import ctypes as C
 import random

@@ -1,5 +1,5 @@
 """Guided self-play at each game's own pace (include/taflhip.h tafl_gselfplay_*): the product's per-game code
-(tafl_guided.hpp Guided::selfplay_step, compiled for the host in tests/hostsim_gselfplay) against the oracle loop - orc.GameLogic.gmcts,
+(tafl_guided.hpp Guided::selfplay_step, compiled for the host in tests/hostsim) against the oracle loop - orc.GameLogic.gmcts,
 then examples_util.pick_rule with examples_util.sample_word, then the oracle's do_play - per game and move.  The evaluator is
 tests/stub_net.stub_predict with a per-game salt.  Every comparison is exact.  CPU only."""
 import ctypes as C
