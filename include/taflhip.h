@@ -370,7 +370,10 @@ int tafl_mcts_play_best(tafl_batch* b, tafl_play* out_plays, tafl_effects* out_e
  * exactly `for m in 0..n_moves: tafl_mcts_run(sim_offset + m * n_sims); tafl_mcts_play_best` - but a game starts its next search as soon
  * as ITS OWN search is done, so the games of the batch are at different phases of their searches and the device stays full (a batch of
  * synchronous searches ends every search in a tail of nearly empty rounds).  Games that end stop searching; out_plays[m * n + g] (may be
- * NULL) is the play game g made at move m, all-zero once its game was over.  tafl_mcts_get_stats afterwards covers all searches. */
+ * NULL) is the play game g made at move m, all-zero once its game was over.  tafl_mcts_get_stats afterwards covers all searches: a game
+ * that ends inside the run is not searched again, and a game that is already over when the run begins is searched ONCE from its terminal
+ * root (n_sims simulations, all of them terminal_hits, as tafl_mcts_run books them), makes no play and stops - so an episode played in
+ * several runs books n_sims more `sims` per finished game and run than the same episode in one run; plays, states and examples are the same. */
 int tafl_selfplay_run(tafl_batch* b, const tafl_mcts_params* params, uint32_t n_moves, uint64_t game_id_base, tafl_play* out_plays);
 /* Subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE).  tafl_mcts_advance plays actions[g] (a dense action index, tafl_action_encode order) in game g
  * with do_valid_play, exactly as tafl_step, and makes the child (root, action) the root of the retained tree: every statistic below it is

@@ -122,25 +122,27 @@ def z_of(state: TaflState, side):
 
 
 def oracle_record(orc, lg, states, G, wb, sims, cap, cpuct, seed, base, n_moves, sample_seed, temp_moves, move_base=0, sim_offset=0,
-                  max_children=256, ids=None):
+                  max_children=256, ids=None, workers=0):
     """The loop tafl_selfplay_record replaces, on the oracle.  Per move: orc.batch_mcts (sim_offset + m * sims), the pick by the rule
     restated above, the example from GameState.board_to_matrix() and the visited root children, orc.batch_step.  `states` is advanced in
-    place.  ids: global game ids per state (default base + g).  Returns (plays [m][g], examples per game, info) with
-    info = {non_argmax, game_moves, widest}."""
+    place.  ids: global game ids per state (default base + g).  workers: the searches of a move run game by game, side by side on that
+    many host threads (the same children: a search is a function of its position and its global id).  Returns (plays [m][g], examples
+    per game, info) with info = {non_argmax, game_moves, widest, searches}; searches: the (game, move) pairs whose game was ONGOING."""
     n = states[0].side_len
     plays_all, ex = [], [[] for _ in range(G)]
-    info = {"non_argmax": 0, "game_moves": 0, "widest": 0}
+    info = {"non_argmax": 0, "game_moves": 0, "widest": 0, "searches": 0}
     for m in range(n_moves):
         p = TaflMctsParams(sims, cap, cpuct, seed, sim_offset + m * sims, 0)
-        if ids is None:
+        info["searches"] += sum(states[g].status == abi.ONGOING for g in range(G))
+        if ids is None and not workers:
             kids, cnt, _ = orc.batch_mcts(lg, states, G, wb, p, base, max_children)
         else:
-            jobs = [(g, states[g], ids[g]) for g in range(G)]
-            per = pu.oracle_children_parallel(orc, lg, wb, p, jobs, max_children)
+            jobs = [(g, states[g], ids[g] if ids is not None else base + g) for g in range(G)]
+            per = pu.oracle_children_parallel(orc, lg, wb, p, jobs, max_children, workers or 16)
         sub = (TaflPlay * G)()
         row = []
         for g in range(G):
-            if ids is None:
+            if ids is None and not workers:
                 ch = [(kids[g * max_children + j].action, kids[g * max_children + j].visits) for j in range(cnt[g])]
             else:
                 ch = [(a, v) for a, v, _ in per[g]]

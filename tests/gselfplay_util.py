@@ -133,6 +133,44 @@ def host_run(rules, n, wb, states, S, c_puct, salts, n_moves, sample_seed, temp_
     return out, list(faults), rounds
 
 
+def device_examples(ex, G, n):
+    """(examples per game as examples_util.Example.fields() tuples, overflow marks per game) read back from the device."""
+    lens, total = ex.counts()
+    lens = list(lens)
+    assert total == sum(lens)
+    idx = np.array([j * G + g for g in range(G) for j in range(lens[g])], np.uint32)
+    out, over = [[] for _ in range(G)], [[] for _ in range(G)]
+    if idx.size:
+        nc, ov, pl, mv, acts, vis = ex.read(idx)
+        boards, sides, _pi, _z, _fin = ex.gather(idx)
+        for i, e in enumerate(idx):
+            g, k = int(e) % G, int(nc[i])
+            out[g].append((boards[i].tolist(), int(sides[i]), acts[i, :k].tolist(), vis[i, :k].tolist(), int(pl[i]), int(mv[i])))
+            over[g].append(int(ov[i]))
+    return out, over
+
+
+def device_run(batch, ex, n, S, c_puct, salts, n_moves, sample_seed, temp_moves, move_base=0, base=0, edges_per_node=256):
+    """tafl_gselfplay_begin / the step loop / tafl_gselfplay_end through the C-ABI on `batch` (states uploaded), with the stub network in
+    host buffers.  Returns (Run with the examples read from `ex`, overflow marks per game, stats)."""
+    G, A = batch.n, abi.action_size(n)
+    batch.gselfplay_begin(ex, n_moves, S, c_puct, edges_per_node, game_id_base=base, sample_seed=sample_seed, temp_moves=temp_moves, move_base=move_base)
+    w = batch.gselfplay_step()
+    while w:
+        boards, sides, waiting = batch.gmcts_leaves()
+        assert sum(waiting) == w
+        pri, val = stub_rows(boards, sides, waiting, G, n, A, salts)
+        w = batch.gselfplay_step(fptr(pri), fptr(val))
+    plays, moves = batch.gselfplay_end()
+    stats = batch.gmcts_stats()
+    st = batch.download()
+    run = Run(G, n_moves)
+    run.plays = [[pu.play_tuple4(plays[m * G + g]) for g in range(G)] for m in range(n_moves)]
+    run.states, run.moves, run.sims = [bytes(st[g]) for g in range(G)], list(moves), stats.sims
+    run.examples, over = device_examples(ex, G, n)
+    return run, over, stats
+
+
 def fates(states_before, run):
     """(games over at the start, games that ended during the run, games still going after it)."""
     G = len(states_before)

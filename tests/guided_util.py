@@ -19,6 +19,26 @@ def stub_batch(boards, sides, waiting, n, side_len, action_size, salts):
     return pri, val
 
 
+def run_device_guided(batch, n, side_len, n_sims, c_puct, salts, edges_per_node=256, max_children=600, keep=False):
+    """The same loop through the C-ABI (tafl_gmcts_begin / step / leaves / root_children): (children per game, stats, rounds).
+    keep: n_sims more simulations on the retained tree."""
+    from alphazeroforhnefatafl_amd import abi
+    A = abi.action_size(side_len)
+    batch.gmcts_begin(n_sims, edges_per_node, keep)
+    w = batch.gmcts_step(None, None, c_puct, n_sims)
+    rounds = 0
+    while w:
+        boards, sides, waiting = batch.gmcts_leaves()
+        assert sum(waiting) == w
+        pri, val = stub_batch(boards, sides, waiting, n, side_len, A, salts)
+        w = batch.gmcts_step(pri, val, c_puct, n_sims)
+        rounds += 1
+    kids, cnt = batch.gmcts_root_children(max_children)
+    out = [[(kids[g * max_children + i].action, kids[g * max_children + i].visits, float(kids[g * max_children + i].q).hex()) for i in range(cnt[g])]
+           for g in range(n)]
+    return out, batch.gmcts_stats(), rounds
+
+
 def run_hostsim_guided(hs, L, states, n, n_sims, c_puct, salts, edges_per_node=256, max_children=600):
     from alphazeroforhnefatafl_amd import abi
     A = abi.action_size(hs.n)

@@ -50,44 +50,16 @@ def batch_of(glg, states, first, count):
     return b
 
 
-def device_examples(ex, G, n):
-    """(examples per game as examples_util.Example.fields() tuples, overflow marks per game) read back from the device."""
-    lens, total = ex.counts()
-    lens = list(lens)
-    assert total == sum(lens)
-    idx = np.array([j * G + g for g in range(G) for j in range(lens[g])], np.uint32)
-    out, over = [[] for _ in range(G)], [[] for _ in range(G)]
-    if idx.size:
-        nc, ov, pl, mv, acts, vis = ex.read(idx)
-        boards, sides, _pi, _z, _fin = ex.gather(idx)
-        for i, e in enumerate(idx):
-            g, k = int(e) % G, int(nc[i])
-            out[g].append((boards[i].tolist(), int(sides[i]), acts[i, :k].tolist(), vis[i, :k].tolist(), int(pl[i]), int(mv[i])))
-            over[g].append(int(ov[i]))
-    return out, over
+device_examples = gsu.device_examples
 
 
 def own_pace_run(glg, states, first, G, n, S, salts, n_moves, temp_moves, base, max_children=None):
     """The run through tafl_gselfplay_* with the stub network in host buffers: (Run with its examples, overflow marks, stats)."""
-    A = abi.action_size(n)
     b = batch_of(glg, states, first, G)
     ex = glg.new_examples(G, n_moves, max_children or S)
-    b.gselfplay_begin(ex, n_moves, S, CPUCT, game_id_base=base, sample_seed=SEED, temp_moves=temp_moves)
-    w = b.gselfplay_step()
-    while w:
-        boards, sides, waiting = b.gmcts_leaves()
-        assert sum(waiting) == w
-        pri, val = gsu.stub_rows(boards, sides, waiting, G, n, A, salts[first:first + G])
-        w = b.gselfplay_step(gsu.fptr(pri), gsu.fptr(val))
-    plays, moves = b.gselfplay_end()
-    stats = b.gmcts_stats()
-    st = b.download()
-    run = gsu.Run(G, n_moves)
-    run.plays = [[pu.play_tuple4(plays[m * G + g]) for g in range(G)] for m in range(n_moves)]
-    run.states, run.moves, run.sims = [bytes(st[g]) for g in range(G)], list(moves), stats.sims
-    run.examples, over = device_examples(ex, G, n)
+    out = gsu.device_run(b, ex, n, S, CPUCT, salts[first:first + G], n_moves, SEED, temp_moves, base=base)
     ex.close(); b.close()
-    return run, over, stats
+    return out
 
 
 def whole(cfg):

@@ -19,21 +19,7 @@ with open(os.path.join(HERE, "golden", "mcts_golden.json")) as f:
     GOLD = json.load(f)
 
 
-def run_device_guided(batch, n, side_len, n_sims, c_puct, salts, edges_per_node=256, max_children=600):
-    A = abi.action_size(side_len)
-    batch.gmcts_begin(n_sims, edges_per_node)
-    w = batch.gmcts_step(None, None, c_puct, n_sims)
-    rounds = 0
-    while w:
-        boards, sides, waiting = batch.gmcts_leaves()
-        assert sum(waiting) == w
-        pri, val = gu.stub_batch(boards, sides, waiting, n, side_len, A, salts)
-        w = batch.gmcts_step(pri, val, c_puct, n_sims)
-        rounds += 1
-    kids, cnt = batch.gmcts_root_children(max_children)
-    out = [[(kids[g * max_children + i].action, kids[g * max_children + i].visits, float(kids[g * max_children + i].q).hex()) for i in range(cnt[g])]
-           for g in range(n)]
-    return out, batch.gmcts_stats(), rounds
+run_device_guided = gu.run_device_guided
 
 
 @pytest.mark.parametrize("case", GOLD["guided_cases"], ids=[c["name"] for c in GOLD["guided_cases"]])
