@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRules,
+from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -83,6 +83,9 @@ SYMBOLS = [
     ("tafl_gselfplay_begin", _i32, [_vp, _u32, _u32, _dbl, _P(TaflSelfplayOpts), _u32, _u64, _vp]),
     ("tafl_gselfplay_step", _i32, [_vp, _vp, _vp, _i32, _P(_u32)]),
     ("tafl_gselfplay_end", _i32, [_vp, _P(TaflPlay), _P(_u32)]),
+    ("tafl_gmcts_set_root_noise", _i32, [_vp, _P(TaflRootNoise)]),
+    ("tafl_root_noise_eval", _i32, [_vp, _P(TaflRootNoise), _vp, _i32]),
+    ("tafl_gmcts_root_priors", _i32, [_vp, _vp, _i32]),
     ("tafl_replay_append", _i32, [C.c_char_p, _P(_u8), _u8, _P(_u8), _u32, _u8, _u8, _u64]),
     ("tafl_replay_append_batch", _i32, [C.c_char_p, _P(_u8), _u8, _u32, _P(_u8), _P(_u32), _P(_u8), _P(_u8), _u64]),
     ("tafl_replay_read", _i32, [C.c_char_p, _u8, _u32, _P(_u8), _P(_u8), _u32, _P(_u32), _P(_u8), _P(_u8), _P(_u32)]),

@@ -158,18 +158,26 @@ class TaflSelfplayOpts(C.Structure):
                 ("_reserved", C.c_uint32 * 3)]
 
 
+class TaflRootNoise(C.Structure):
+    """tafl_root_noise: Dirichlet noise at the root of a guided search (tafl_gmcts_set_root_noise, tafl_root_noise_eval)."""
+    _fields_ = [("alpha", C.c_double), ("epsilon", C.c_double), ("seed", C.c_uint64), ("game_id_base", C.c_uint64), ("move_no", C.c_uint32),
+                ("flags", C.c_uint32), ("_reserved", C.c_uint64)]
+
+
 class TaflExamplesStats(C.Structure):
     _fields_ = [("dropped", C.c_uint64), ("overflowed", C.c_uint64), ("bad_index", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
-                  "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32}
+                  "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
+                  "tafl_root_noise": 48}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
                     ("tafl_mcts_stats", TaflMctsStats), ("tafl_gmcts_stats", TaflGmctsStats),
-                    ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats)]:
+                    ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats),
+                    ("tafl_root_noise", TaflRootNoise)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

@@ -28,6 +28,34 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_step(Consts<NL> C, GuidedM
     Guided<NL, W>::step(M, g, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, C, gs);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+// the same round with Dirichlet noise mixed into the root priors (tafl_root_noise; nz.gid holds the game id base): instantiations of their
+// own, chosen at launch, so that the kernels above stay as they are
+template <int NL, int W, bool NOISE>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_step(Consts<NL> C, GuidedMem M, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                           uint32_t n_sims, unsigned long long* stats, RootNoise nz) {
+    static_assert(NOISE, "the noise-free round is k_gmcts_step<NL, W>");
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    nz.gid += g;
+    Guided<NL, W>::step(M, g, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, C, gs, nz);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
+// eta for every game's batch state (tafl_root_noise_eval) and the dense root priors (tafl_gmcts_root_priors); `out` is zeroed before
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_root_noise_eval(Consts<NL> C, const Quad* soa, uint32_t n, RootNoise nz, double* out, uint32_t A) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= n) return;
+    DState<NL> st; StateIO<NL>::load_soa(soa, n, g, st);
+    nz.gid += g;
+    Guided<NL, W>::noise_row(st, C, nz, out + (size_t)g * A);
+}
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_root_priors(Consts<NL> C, GuidedMem M, double* out, uint32_t A) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    Guided<NL, W>::root_priors(M, g, out + (size_t)g * A);
+}
 // network input of the waiting leaves: board_to_matrix planes (game/main.rs:55-83), side to move, waiting flag; one thread per tile
 template <int NL, int W>
 __global__ __launch_bounds__(256) void k_gmcts_leaves(Consts<NL> C, GuidedMem M, uint8_t* boards, uint8_t* sides, uint8_t* waiting) {
@@ -139,6 +167,16 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_step(Consts<NL> C, Gui
     Guided<NL, W>::selfplay_step(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, rec, C, gs);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+template <int NL, int W, bool NOISE>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_step(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                               uint32_t n_sims, GSelfPlay sp, SelfPlayRec rec, unsigned long long* stats, RootNoise nz) {
+    static_assert(NOISE, "the noise-free round is k_gselfplay_step<NL, W>");
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::selfplay_step(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, rec, C, gs, nz);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
 
 // the arena of a search from fresh roots: max_sims + 1 nodes and (max_sims + 1) x edges_per_node edges per game; the guided stats are zeroed
 static int gmcts_arena(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, const char* name) {
@@ -178,7 +216,56 @@ static int gmcts_waiting(tafl_batch* b, uint32_t* out_waiting) {
     return TAFL_OK;
 }
 
+// a tafl_root_noise the library accepts
+static int noise_check(const tafl_root_noise* cfg, const char* name) {
+    if (!(cfg->alpha > 0.0) || !(cfg->alpha < INFINITY) || !(cfg->epsilon > 0.0) || !(cfg->epsilon <= 1.0))
+        return fail(TAFL_ERR_INVALID_ARG, std::string(name) + ": alpha must be positive and finite, epsilon in (0, 1]");
+    if (cfg->flags != 0 || cfg->_reserved != 0) return fail(TAFL_ERR_UNSUPPORTED, std::string(name) + ": flags and the reserved word must be 0");
+    return TAFL_OK;
+}
+static RootNoise noise_arg(const tafl_root_noise& cfg) {
+    RootNoise nz; nz.alpha = cfg.alpha; nz.epsilon = cfg.epsilon; nz.seed = cfg.seed; nz.gid = cfg.game_id_base; nz.move_no = cfg.move_no;
+    return nz;
+}
+
 extern "C" {
+
+int tafl_gmcts_set_root_noise(tafl_batch* b, const tafl_root_noise* cfg) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_set_root_noise: null batch");
+    if (!cfg) { b->noise_set = false; return TAFL_OK; }
+    if (const int rc = noise_check(cfg, "tafl_gmcts_set_root_noise")) return rc;
+    b->noise_set = true; b->noise_cfg = *cfg;
+    return TAFL_OK;
+}
+
+int tafl_root_noise_eval(tafl_batch* b, const tafl_root_noise* cfg, double* out_eta, int out_is_device) {
+    if (!b || !cfg || !out_eta) return fail(TAFL_ERR_INVALID_ARG, "tafl_root_noise_eval: null argument");
+    if (const int rc = noise_check(cfg, "tafl_root_noise_eval")) return rc;
+    if (const int rc = join_search(b)) return rc;
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c); const size_t count = (size_t)n * A;
+    HIPCHK(hipSetDevice(c->device));
+    double* d;
+    STAGED(d, b->policy, out_eta, count, out_is_device);
+    HIPCHK(hipMemsetAsync(d, 0, sizeof(double) * count, c->stream));
+    const RootNoise nz = noise_arg(*cfg);
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_root_noise_eval<t.NL, t.W>), c, n, t.CC, b->soa, n, nz, d, A); });
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) COPY_OUT(out_eta, d, count, c->stream);
+    return sync_ok(c);
+}
+
+int tafl_gmcts_root_priors(tafl_batch* b, double* out, int out_is_device) {
+    if (!b || !b->g_has || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_root_priors: bad argument");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c); const size_t count = (size_t)n * A;
+    HIPCHK(hipSetDevice(c->device));
+    double* d;
+    STAGED(d, b->policy, out, count, out_is_device);
+    HIPCHK(hipMemsetAsync(d, 0, sizeof(double) * count, c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_root_priors<t.NL, t.W>), c, n, t.CC, b->gmem, d, A); });
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) COPY_OUT(out, d, count, c->stream);
+    return sync_ok(c);
+}
 
 int tafl_gmcts_begin(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node) { return tafl_gmcts_begin_ex(b, max_sims, edges_per_node, 0); }
 
@@ -205,8 +292,11 @@ static int gmcts_begin_keep(tafl_batch* b, uint32_t max_sims, uint32_t edges_per
 int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, uint32_t flags) {
     if (!b || max_sims == 0 || edges_per_node == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_begin: bad argument");
     if (flags & ~(uint32_t)TAFL_GMCTS_KEEP_TREE) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: unknown flags");
+    if ((flags & TAFL_GMCTS_KEEP_TREE) && b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: root noise on a retained tree is not supported (tafl_gmcts_set_root_noise(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     b->gsp_active = false;                                   // (a guided self-play run on this arena is closed)
+    b->g_noise_on = b->noise_set;                            // the search latches the noise setting
+    if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     HIPCHK(hipSetDevice(c->device));
     if (flags & TAFL_GMCTS_KEEP_TREE) { if (const int rc = join_search(b)) return rc; }
     if ((flags & TAFL_GMCTS_KEEP_TREE) && b->g_has && b->g_tree_live) {
@@ -233,7 +323,8 @@ int tafl_gmcts_step(tafl_batch* b, const float* priors, const float* values, int
     if (const int rc = stage_evaluation(b, priors, values, in_is_device)) return rc;
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st); });
+    if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st, b->g_noise); });
+    else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st); });
     HIPCHK(hipGetLastError());
     return gmcts_waiting(b, out_waiting);
 }
@@ -342,7 +433,8 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st); });
+    if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st, b->g_noise); });
+    else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st); });
     HIPCHK(hipGetLastError());
     return TAFL_OK;
 }
@@ -368,6 +460,8 @@ int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node
     if (ex) b->gsp_rec.ex = ex->mem;
     b->gsp_rec.sample_seed = o->sample_seed; b->gsp_rec.game_id_base = game_id_base; b->gsp_rec.temp_moves = o->temp_moves; b->gsp_rec.move_base = o->move_base;
     b->gsp_sims = n_sims; b->gsp_cpuct = c_puct;
+    b->g_noise_on = b->noise_set;                            // the run latches the noise setting; gid and M are the run's own
+    if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     HIPCHK(hipMemsetAsync(b->gsp_plays.p, 0, sizeof(tafl_play) * (size_t)n * n_moves, c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_init<t.NL, t.W>), c, n, t.CC, b->soa, b->gmem, b->gsp); });
     HIPCHK(hipGetLastError());

@@ -16,6 +16,9 @@
 // Storage differs from the rollout mode (tafl_ops.hpp): with non-uniform priors the visited children are no longer a prefix
 // of the legal list, so a node owns one edge per LEGAL move, in canonical (= ascending action index) order.
 //
+// Dirichlet noise at the root (include/taflhip.h tafl_root_noise) is a tail of the root's expansion, compiled only into
+// the NOISE instantiations (step / selfplay_step with a RootNoise argument); the functions without it are what they were.
+//
 // A guided self-play run records its examples and draws its plays with the functions of tafl_examples.hpp (example_append,
 // visit_draw, which own the example layout and the board encoding); this file only walks the root's edge block for them.
 #pragma once
@@ -58,6 +61,53 @@ struct GSelfPlay {
     tafl_play* plays;            // [m * G + g] the play of move m (all-zero: not made)
     uint32_t n_moves;
 };
+// Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
+struct RootNoise {
+    double alpha, epsilon;
+    uint64_t seed, gid;          // gid = game_id_base + g
+    uint32_t move_no;            // M
+};
+constexpr uint32_t kNoiseTries = 16;         // rejection rounds of one Gamma variate before its fallback
+constexpr uint32_t kNoiseWordsPerTry = 5;    // uniform words one round consumes; the words of the boost follow at kNoiseTries * kNoiseWordsPerTry
+
+// the uniform word `draw` of the noise stream of (seed, gid, M, action a): the taflmix32 family of tafl_core.hpp.  The game key is that of
+// selfplay_rand with kNoiseKey folded in, so for equal seeds the two streams hang off different game keys; below it one simulation key per
+// move number, one per action, and the draw index as the ply.
+constexpr uint64_t kNoiseKey = 0x4449524943484C45ull;
+static TAFL_HD uint32_t noise_word(uint32_t ak, uint32_t draw) { return Engine<2, 7>::ply_rand(ak, draw); }
+static TAFL_HD uint32_t noise_action_key(const RootNoise& nz, uint32_t a) {
+    using E = Engine<2, 7>;
+    const uint32_t mk = E::sim_key(E::game_key(nz.seed, nz.gid) ^ kNoiseKey, nz.move_no);
+    return E::sim_key((uint64_t)mk | ((uint64_t)E::fmix32(mk + 0x9E3779B9u) << 32), a);
+}
+// a uniform in (0, 1) with 53 random bits from two words: ((w0 >> 5) * 2^26 + (w1 >> 6) + 0.5) * 2^-53
+static TAFL_HD double noise_uniform(uint32_t w0, uint32_t w1) { return ((double)(w0 >> 5) * 67108864.0 + (double)(w1 >> 6) + 0.5) * (1.0 / 9007199254740992.0); }
+// One Gamma(alpha, 1) variate, a pure function of (seed, gid, M, a).  Marsaglia & Tsang (2000) for shape k = alpha (alpha >= 1) or
+// alpha + 1 (alpha < 1, then multiplied by U^(1/alpha)): d = k - 1/3, c = 1/sqrt(9 d); a round draws a normal x (Box-Muller: words 0-2)
+// and a uniform u (words 3-4), v = (1 + c x)^3, and accepts d v when v > 0 and log u < x^2/2 + d - d v + d log v.  A round accepts with
+// probability > 0.95 for every d >= 2/3; after kNoiseTries rounds without one the variate is d (v = 1): probability < 0.05^16 < 2e-21.
+// For small alpha the boost exp(log U / alpha) underflows to 0 for most actions, which is a valid value.
+static TAFL_HD double noise_gamma(const RootNoise& nz, uint32_t a) {
+    const uint32_t ak = noise_action_key(nz, a);
+    const bool boost = nz.alpha < 1.0;
+    const double d = (boost ? nz.alpha + 1.0 : nz.alpha) - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    double g = d;
+    for (uint32_t t = 0; t < kNoiseTries; ++t) {
+        const uint32_t w = t * kNoiseWordsPerTry;
+        const double r = sqrt(-2.0 * log(noise_uniform(noise_word(ak, w), noise_word(ak, w + 1u))));
+        const double x = r * cos(6.283185307179586 * (((double)noise_word(ak, w + 2u) + 0.5) * (1.0 / 4294967296.0)));
+        const double u = noise_uniform(noise_word(ak, w + 3u), noise_word(ak, w + 4u));
+        const double t1 = 1.0 + c * x, v = t1 * t1 * t1;
+        if (v > 0.0 && log(u) < 0.5 * x * x + d - d * v + d * log(v)) { g = d * v; break; }
+    }
+    if (boost) {
+        const uint32_t w = kNoiseTries * kNoiseWordsPerTry;
+        g = g * exp(log(noise_uniform(noise_word(ak, w), noise_word(ak, w + 1u))) / nz.alpha);
+    }
+    return g;
+}
+// eta_i from gamma_i, the sequential sum s of the root's variates and the number n of its legal actions
+static TAFL_HD double noise_eta(double gamma, double s, uint32_t n) { return (s > 0.0 && s < __builtin_inf()) ? gamma / s : 1.0 / (double)n; }
 
 template <int NL, int W>
 struct Guided {
@@ -136,7 +186,11 @@ struct Guided {
     }
 
     // mcts.py:83-102 for the pending leaf, with the network's answer
-    static TAFL_HD bool expand(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C) {
+    static TAFL_HD bool expand(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C) { return expand_as<false>(M, g, priors, A, C, nullptr); }
+    // NOISE: when the leaf is node 0, P' = (1 - epsilon) P + epsilon eta (tafl_root_noise): the raw variates wait in the fresh edges' q
+    // between the two passes
+    template <bool NOISE>
+    static TAFL_HD bool expand_as(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C, const RootNoise* nz) {
         const uint32_t L = M.leaf[g];
         S st; IO::load_rec(M.node_state + ((size_t)L * M.G + g) * IO::QUADS, st);
         const uint32_t base = M.edge_top[g];
@@ -157,6 +211,14 @@ struct Guided {
             const double s2 = np_sum_sparse(e, cnt, A, true);
             for (uint32_t i = 0; i < cnt; ++i) e[i].p = (e[i].p + 1.0) / s2;
         }
+        if constexpr (NOISE) {
+            if (L == 0) {
+                double s = 0.0;
+                for (uint32_t i = 0; i < cnt; ++i) { const double gm = noise_gamma(*nz, e[i].action); e[i].q = gm; s += gm; }
+                const double keep = 1.0 - nz->epsilon;
+                for (uint32_t i = 0; i < cnt; ++i) { e[i].p = keep * e[i].p + nz->epsilon * noise_eta(e[i].q, s, cnt); e[i].q = 0.0; }
+            }
+        }
         GNode* h = &M.hdr[(size_t)L * M.G + g];
         h->edge_base = base; h->n_legal = (uint16_t)cnt; h->ns = 0; h->expanded = 1;
         M.edge_top[g] = base + cnt;
@@ -165,11 +227,17 @@ struct Guided {
 
     // One round for game g.  `priors` = this game's row of the network output (may be null when nothing is pending).
     static TAFL_HD void step(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                             const K& C, GuidedStats& gs) {
+                             const K& C, GuidedStats& gs) { step_as<false>(M, g, priors, value, A, c_puct, n_sims, C, gs, nullptr); }
+    // the round with the root noise `nz` of this game's search
+    static TAFL_HD void step(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                             const K& C, GuidedStats& gs, const RootNoise& nz) { step_as<true>(M, g, priors, value, A, c_puct, n_sims, C, gs, &nz); }
+    template <bool NOISE>
+    static TAFL_HD void step_as(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                const K& C, GuidedStats& gs, const RootNoise* nz) {
         if (M.fault[g]) { M.kind[g] = 3; return; }
         uint32_t sims = M.sims_done[g];
         if (M.kind[g] == 1) {
-            if (!priors || !expand(M, g, priors, A, C)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
+            if (!priors || !expand_as<NOISE>(M, g, priors, A, C, nz)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
             gs.predicts += 1;
             backup(M, g, M.leaf[g], -(double)value);              // return -v (mcts.py:102) into the callers
             ++sims; gs.sims += 1;
@@ -273,6 +341,25 @@ struct Guided {
         for (uint32_t j = 0; j < n; ++j) dst[(size_t)g * M.edge_cap + j] = M.edges[(size_t)g * M.edge_cap + j];
     }
 
+    // the dense row eta that a search from `st` under `nz` mixes into its root priors: zero off the legal actions, all zero for a game
+    // that is over; the variates wait in the row between the two passes
+    static TAFL_HD void noise_row(const S& st, const K& C, const RootNoise& nz, double* row) {
+        if (O::term_code(st)) return;
+        const uint32_t side = st.flags & TAFL_F_SIDE;
+        Move cur = E::canon_start();
+        uint32_t cnt = 0; double s = 0.0;
+        while (E::canon_next(st, side, C, cur)) { const uint32_t a = O::action_of(cur, C); const double gm = noise_gamma(nz, a); row[a] = gm; s += gm; ++cnt; }
+        cur = E::canon_start();
+        while (E::canon_next(st, side, C, cur)) { const uint32_t a = O::action_of(cur, C); row[a] = noise_eta(row[a], s, cnt); }
+    }
+    // the dense Ps[root] as the root's edges hold it (nothing is written for a root that is not expanded)
+    static TAFL_HD void root_priors(const GuidedMem& M, uint32_t g, double* row) {
+        const GNode h = M.hdr[g];
+        if (!h.expanded) return;
+        const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
+        for (uint32_t j = 0; j < h.n_legal; ++j) row[eb[j].action] = eb[j].p;
+    }
+
     // visited root edges in ascending action order (mcts.py:40-41)
     static TAFL_HD uint32_t root_children(const GuidedMem& M, uint32_t g, tafl_root_child* out, uint32_t max_children) {
         const GNode h = M.hdr[g];
@@ -309,11 +396,24 @@ struct Guided {
     // (= do_valid_play) when the edge was first visited.  A game that faults, is over, has no visited root edge or has made n_moves moves stops.
     static TAFL_HD void selfplay_step(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                       const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs) {
+        selfplay_step_as<false>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, nullptr);
+    }
+    // the round with root noise: alpha, epsilon and seed of `nz`; gid and M are the run's (rec.game_id_base + g, rec.move_base + moves made)
+    static TAFL_HD void selfplay_step(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                      const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz) {
+        selfplay_step_as<true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, &nz);
+    }
+    template <bool NOISE>
+    static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                         const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz) {
         uint32_t md = sp.moves_done[g];
         if (md & kGspStopped) return;
+        // (only the first pass of the loop below expands a leaf, so the move number of the search that is open now serves the whole call)
+        RootNoise mine;
+        if constexpr (NOISE) { mine = *nz; mine.gid = rec.game_id_base + g; mine.move_no = rec.move_base + md; }
         // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
         for (;;) {
-            step(M, g, priors, value, A, c_puct, n_sims, C, gs);
+            step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr);
             if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
             if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
             const GNode h = M.hdr[g];

@@ -210,6 +210,9 @@ struct tafl_batch {
     bool gsp_active = false, gsp_first = false, gsp_has = false;
     GSelfPlay gsp = {}; SelfPlayRec gsp_rec = {}; uint32_t gsp_sims = 0; double gsp_cpuct = 0.0;
     DevBuf gsp_moves_done, gsp_plays;
+    // Dirichlet noise at the root (tafl_gmcts_set_root_noise): the setting, and what the open search or run latched at its begin
+    bool noise_set = false, g_noise_on = false;
+    tafl_root_noise noise_cfg = {}; RootNoise g_noise = {};
     // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
     // arena and the id map of a re-root; a small read-back buffer
     bool tree_live = false, g_tree_live = false;

@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
 
 KC_MOVEGEN, KC_STEP, KC_ROLLOUT, KC_MCTS_TREE, KC_MCTS_ROLLOUT = range(5)
@@ -354,6 +354,35 @@ class GameBatch:
         moves = (C.c_uint32 * self.n)()
         check(lib().tafl_gselfplay_end(self._h, plays, moves))
         return plays, moves
+
+    # -- Dirichlet noise at the root of a guided search (include/taflhip.h tafl_root_noise) ----------------------------------
+    def set_root_noise(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0):
+        """P' = (1 - epsilon) P + epsilon Dir(alpha) at the root of every later gmcts_begin search and gselfplay run (latched at the
+        begin).  `game_id_base` / `move_no` key a lock-step search; a gselfplay run uses its own game ids and move numbers."""
+        cfg = TaflRootNoise(alpha, epsilon, seed, game_id_base, move_no, 0, 0)
+        check(lib().tafl_gmcts_set_root_noise(self._h, C.byref(cfg)))
+
+    def clear_root_noise(self):
+        check(lib().tafl_gmcts_set_root_noise(self._h, None))
+
+    def root_noise_eval(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0, out_device_ptr: int | None = None):
+        """eta of tafl_root_noise_eval for every game's current state: float64 [n * action_size], zero off the legal actions."""
+        cfg = TaflRootNoise(alpha, epsilon, seed, game_id_base, move_no, 0, 0)
+        if out_device_ptr is not None:
+            check(lib().tafl_root_noise_eval(self._h, C.byref(cfg), C.c_void_p(out_device_ptr), 1))
+            return None
+        out = (C.c_double * (self.n * self.logic.action_size))()
+        check(lib().tafl_root_noise_eval(self._h, C.byref(cfg), C.cast(out, C.c_void_p), 0))
+        return out
+
+    def gmcts_root_priors(self, out_device_ptr: int | None = None):
+        """Dense Ps[root] of the guided search, float64 [n * action_size] (all zero for a root that is not expanded)."""
+        if out_device_ptr is not None:
+            check(lib().tafl_gmcts_root_priors(self._h, C.c_void_p(out_device_ptr), 1))
+            return None
+        out = (C.c_double * (self.n * self.logic.action_size))()
+        check(lib().tafl_gmcts_root_priors(self._h, C.cast(out, C.c_void_p), 0))
+        return out
 
     def mcts_play_best(self, want_results: bool = True):
         """Every game plays the most visited root play of its last search, on the device (tafl_mcts_play_best)."""

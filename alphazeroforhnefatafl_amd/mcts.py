@@ -24,6 +24,19 @@ class MCTSArgs:
     seed: int = 0
     max_rollout_plies: int = 512
     game_id_base: int = 0
+    # Dirichlet noise at the root of a guided search (include/taflhip.h tafl_root_noise); epsilon 0: off.  The rollout mode has no priors
+    # and ignores them.
+    dirichletAlpha: float = 0.0
+    dirichletEpsilon: float = 0.0
+    noiseSeed: int = 0
+
+
+def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
+    """The batch's root-noise setting as `args` asks for it: set, or cleared when dirichletEpsilon is 0."""
+    if args.dirichletEpsilon:
+        batch.set_root_noise(args.dirichletAlpha, args.dirichletEpsilon, args.noiseSeed, args.game_id_base, move_no)
+    else:
+        batch.clear_root_noise()
 
 
 class MCTS:
@@ -74,14 +87,15 @@ class GuidedMCTS:
     """
 
     def __init__(self, batch: GameBatch, nnet, args: MCTSArgs, edges_per_node: int = 256, device: bool = False, buffers=None,
-                 keep_tree: bool = False):
-        self.batch, self.nnet, self.args, self.keep_tree = batch, nnet, args, keep_tree
+                 keep_tree: bool = False, move_no: int = 0):
+        self.batch, self.nnet, self.args, self.keep_tree, self.move_no = batch, nnet, args, keep_tree, move_no
         self.edges_per_node, self.device, self.buffers = edges_per_node, device, buffers
         self.rounds = 0
         self._ran = False
 
     def search_all(self):
         a, b = self.args, self.batch
+        apply_root_noise(b, a, self.move_no)           # (the noise of move number self.move_no: set it before each search of a game)
         b.gmcts_begin(a.numMCTSSims, self.edges_per_node, keep=self.keep_tree)
         waiting = b.gmcts_step(None, None, a.cpuct, a.numMCTSSims)
         while waiting:

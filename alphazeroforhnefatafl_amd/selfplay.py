@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi import TaflState
 from .engine import Examples, GameBatch
-from .mcts import MCTSArgs
+from .mcts import MCTSArgs, apply_root_noise
 
 
 def _games_over(batch: GameBatch) -> int:
@@ -38,14 +38,16 @@ def play_episodes(batch: GameBatch, examples: Examples, args: MCTSArgs, max_move
 
 
 def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSArgs, max_moves: int, *, sample_seed: int = 1,
-                         temp_moves: int = 0, edges_per_node: int = 256, device: bool = False, buffers=None):
+                         temp_moves: int = 0, edges_per_node: int = 256, device: bool = False, buffers=None, move_base: int = 0):
     """play_episodes with `nnet` as the evaluator (GuidedMCTS's protocol: nnet.predict_batch(boards, sides, waiting) -> (priors, values);
     with device=True `buffers` = (boards_ptr, sides_ptr, waiting_ptr) and everything is a device pointer).  One run of `max_moves` moves
     (tafl_gselfplay_*): every game searches args.numMCTSSims simulations per move at its own pace, so the host loop is leaves -> network
     -> step until nothing waits, with no read-back per move.  Ends with Examples.finalize.  Returns (examples per game, their sum,
-    games that are over)."""
+    games that are over).  args.dirichletEpsilon > 0 mixes Dirichlet(args.dirichletAlpha) noise into every root's priors
+    (include/taflhip.h tafl_root_noise), keyed by args.noiseSeed, the game id and the move number `move_base` + moves made."""
+    apply_root_noise(batch, args)
     batch.gselfplay_begin(examples, max_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=args.game_id_base,
-                          sample_seed=sample_seed, temp_moves=temp_moves)
+                          sample_seed=sample_seed, temp_moves=temp_moves, move_base=move_base)
     waiting = batch.gselfplay_step()
     while waiting:
         if device:

@@ -558,6 +558,57 @@ int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node
 int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, uint32_t* out_waiting);
 int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves);
 
+/* ---- Dirichlet noise at the root of a guided search --------------------------------------------------------------
+ * AlphaZero's root exploration noise, P' = (1 - epsilon) P + epsilon eta with eta ~ Dir(alpha), for tafl_gmcts_* searches from fresh
+ * roots and for tafl_gselfplay_* runs.  Build-defined (the reference has a TODO, src/mcts.rs:53).  Off by default; with it off nothing
+ * in this header behaves differently.
+ *
+ * The root is node 0 of a fresh search.  After its priors P have been masked and normalised (mcts.py:86-98, the all-masked branch
+ * included) let a_0 < ... < a_{n-1} be its legal actions in ascending dense order, gid = game_id_base + game, and M the move number: in a
+ * tafl_gselfplay run opts->move_base + the moves the game has made in the run (and gid from that run's game_id_base), in a lock-step
+ * search cfg->move_no (and cfg->game_id_base).
+ *   words      w(i, k) = ply_rand(ak_i, k), the k-th uniform word of action a_i, with
+ *                  mk   = sim_key(game_key(seed, gid) ^ 0x4449524943484C45, M)
+ *                  ak_i = sim_key(mk | (uint64) fmix32(mk + 0x9E3779B9) << 32, a_i)
+ *              (game_key / sim_key / ply_rand / fmix32 of the taflmix32 family).  The game key differs from the one selfplay_rand's word
+ *              hangs off, so the two streams do not coincide for equal seeds.  A uniform is U(w0, w1) = ((w0 >> 5) * 2^26 + (w1 >> 6) + 0.5)
+ *              * 2^-53, in (0, 1).
+ *   gamma_i    one Gamma(alpha, 1) variate, a pure function of (seed, gid, M, a_i): not of n, the sharding or the lane.  Marsaglia-Tsang
+ *              with shape k = alpha (alpha >= 1) or alpha + 1 (alpha < 1): d = k - 1/3, c = 1 / sqrt(9 d).  Round t = 0 .. 15 draws
+ *              x = sqrt(-2 log U(w(i, 5t), w(i, 5t+1))) * cos(2 pi (w(i, 5t+2) + 0.5) 2^-32), u = U(w(i, 5t+3), w(i, 5t+4)), v = (1 + c x)^3 and
+ *              accepts gamma = d v when v > 0 and log u < x^2 / 2 + d - d v + d log v.  If none of the 16 rounds accepts (probability below
+ *              0.05^16 < 2e-21 per variate) gamma = d.  For alpha < 1 the result is multiplied by exp(log U(w(i, 80), w(i, 81)) / alpha),
+ *              which may underflow to 0.  All in float64 with the math library of the side that runs it (device or host): the last bits of
+ *              gamma are not portable between them, everything else here is.
+ *   s          gamma_0 + gamma_1 + ..., summed sequentially in ascending action order in float64.
+ *   eta_i      gamma_i / s; 1 / n if s is zero or not finite.
+ *   mix        P'_i = (1.0 - epsilon) * P_i + epsilon * eta_i in float64: two multiplications and one addition, no FMA, no second
+ *              renormalisation.
+ * Only node 0 is mixed: the nodes below it are untouched, and a root that is terminal is never expanded and gets no noise.  PUCT, backup,
+ * the pick rule, the example layout and the recorded visit counts are unchanged.
+ *
+ * tafl_gmcts_set_root_noise stores the setting on the batch (cfg == NULL: off).  tafl_gmcts_begin, tafl_gmcts_begin_ex and
+ *   tafl_gselfplay_begin latch it: a change during a search or run takes effect at the next begin.  alpha not positive and finite, or
+ *   epsilon outside (0, 1]: TAFL_ERR_INVALID_ARG; non-zero flags or _reserved: TAFL_ERR_UNSUPPORTED (the setting is left as it was).
+ *   While noise is set, tafl_gmcts_begin_ex(TAFL_GMCTS_KEEP_TREE) fails with TAFL_ERR_UNSUPPORTED: a retained root is already expanded.
+ * tafl_root_noise_eval is stateless and needs no search: for every game's current batch state it writes the dense row out_eta[g * A + a]
+ *   (float64, A = tafl_action_size): eta at the legal actions, 0 elsewhere, all zero for a game that is over - exactly the values a
+ *   search from that state under `cfg` mixes in (the same device function computes both).
+ * tafl_gmcts_root_priors writes the dense Ps[root] [n * A] as the root's edges hold it (after the mix, if any); the row of a root that
+ *   is not expanded is all zero. */
+typedef struct tafl_root_noise {
+    double   alpha;          /* > 0, finite */
+    double   epsilon;        /* 0 < epsilon <= 1 */
+    uint64_t seed;
+    uint64_t game_id_base;   /* lock-step searches; a tafl_gselfplay run uses its own game_id_base */
+    uint32_t move_no;        /* lock-step searches; a tafl_gselfplay run uses opts->move_base + m */
+    uint32_t flags;          /* 0 */
+    uint64_t _reserved;      /* 0 */
+} tafl_root_noise;           /* 48 bytes */
+int tafl_gmcts_set_root_noise(tafl_batch* b, const tafl_root_noise* cfg);
+int tafl_root_noise_eval(tafl_batch* b, const tafl_root_noise* cfg, double* out_eta, int out_is_device);
+int tafl_gmcts_root_priors(tafl_batch* b, double* out, int out_is_device);
+
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
  * with the comma-separated vector, one line value1, one line value2; every line ends in '\n'.

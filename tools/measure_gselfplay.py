@@ -10,7 +10,11 @@ with two evaluators (tools/measure_guided.py): constant priors resident in HBM (
 network.  Both routes play the most visited move (temp_moves = 0), so they play the same games.  One warm-up and `--runs` timed runs per
 line; one JSON line each with min..max seconds, evaluated simulations per second, rounds per move, the mean fraction of the games that
 wait per round (the evaluator's batch fill) and the step's device time per round from events on the library's stream (they bracket the
-8-byte counter memset, the step kernel and the 8-byte read-back of a round)."""
+8-byte counter memset, the step kernel and the 8-byte read-back of a round).
+
+`--noise ALPHA EPS` mixes Dirichlet(ALPHA) noise into every root's priors with weight EPS (tafl_root_noise), seed 1:
+the own-pace run keys it by its own move numbers, the lock-step loop sets the move number before each search, so both still play the
+same games."""
 import argparse
 import ctypes as C
 import json
@@ -30,6 +34,7 @@ def main():
     ap.add_argument("--channels", type=int, default=32)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-conv", action="store_true", help="only the constant-prior evaluator")
+    ap.add_argument("--noise", type=float, nargs=2, metavar=("ALPHA", "EPS"), help="Dirichlet noise at every root (default: off)")
     args = ap.parse_args()
     import numpy as np
     import torch
@@ -93,7 +98,14 @@ def main():
             torch.cuda.synchronize()
             return sum(a.elapsed_time(b) for a, b in self.pairs)
 
+    def noise(b, move_no=0):
+        if args.noise:
+            b.set_root_noise(args.noise[0], args.noise[1], 1, 0, move_no)
+        else:
+            b.clear_root_noise()
+
     def own_pace(b, net, r):
+        noise(b)
         b.gselfplay_begin(None, moves, S, 1.0, epn)
         w = b.gselfplay_step()
         while w:
@@ -118,7 +130,8 @@ def main():
 
     def lock_step(b, net, r):
         sims = 0
-        for _ in range(moves):
+        for m in range(moves):
+            noise(b, m)
             b.gmcts_begin(S, epn)
             w = b.gmcts_step(None, None, 1.0, S)
             while w:
@@ -153,7 +166,7 @@ def main():
                 last = (sims, r, r.step_ms())
             sims, r, ms = last
             final[(name, route)] = bytes(b.download())
-            print(json.dumps({"evaluator": name, "route": route, "games": n, "sims_per_move": S, "moves": moves, "edges_per_node": epn,
+            print(json.dumps({"evaluator": name, "route": route, "games": n, "sims_per_move": S, "moves": moves, "edges_per_node": epn, "noise": args.noise,
                               "seconds_min": round(min(secs), 3), "seconds_max": round(max(secs), 3), "sims": sims,
                               "sims_per_sec_best": sims / min(secs), "sims_per_sec_worst": sims / max(secs),
                               "rounds": r.rounds, "rounds_per_move": r.rounds / moves, "mean_fraction_waiting": r.waiting / max(1, r.rounds) / n,
