@@ -164,6 +164,17 @@ class TaflRootNoise(C.Structure):
                 ("flags", C.c_uint32), ("_reserved", C.c_uint64)]
 
 
+class TaflEpisodeOpts(C.Structure):
+    """tafl_episode_opts: a guided self-play run in episodes (tafl_gselfplay_begin_episodes)."""
+    _fields_ = [("id_stride", C.c_uint64), ("episode_moves", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
+
+
+class TaflEpisodeStats(C.Structure):
+    """tafl_episode_stats: the episodes an episodes run closed, by result, and the ones it cut."""
+    _fields_ = [("attacker_wins", C.c_uint64), ("defender_wins", C.c_uint64), ("draws", C.c_uint64), ("cut", C.c_uint64),
+                ("_reserved", C.c_uint64 * 4)]
+
+
 class TaflExamplesStats(C.Structure):
     _fields_ = [("dropped", C.c_uint64), ("overflowed", C.c_uint64), ("bad_index", C.c_uint64), ("device_bytes", C.c_uint64)]
 
@@ -171,13 +182,14 @@ class TaflExamplesStats(C.Structure):
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
                   "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
-                  "tafl_root_noise": 48}
+                  "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
                     ("tafl_mcts_stats", TaflMctsStats), ("tafl_gmcts_stats", TaflGmctsStats),
                     ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats),
-                    ("tafl_root_noise", TaflRootNoise)]:
+                    ("tafl_root_noise", TaflRootNoise), ("tafl_episode_opts", TaflEpisodeOpts),
+                    ("tafl_episode_stats", TaflEpisodeStats)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

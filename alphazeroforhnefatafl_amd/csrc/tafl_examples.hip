@@ -1,18 +1,14 @@
 // tafl_examples.hip — training examples recorded on the device: k_examples_*, tafl_examples_* and tafl_selfplay_record.
 #include "tafl_internal.hpp"
 
-// z and the final mark of every recorded example, from the CURRENT status of its game in the batch (tafl_examples_finalize): one lane per game
+// z and the final mark of every recorded example whose result is open (all of them, unless an episodes run has closed some), from the
+// CURRENT status of its game in the batch (tafl_examples_finalize): one lane per game
 template <int NL>
-__global__ __launch_bounds__(TAFL_BLOCK) void k_examples_finalize(const Quad* soa, ExamplesMem X) {
+__global__ __launch_bounds__(TAFL_BLOCK) void k_examples_finalize(const Quad* soa, ExamplesMem X, const uint32_t* open_from) {
     const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
     if (g >= X.G) return;
     const uint32_t flags = soa[(size_t)((2 * NL + 4) / 4) * X.G + g].w;
-    const uint32_t len = X.len[g] < X.max_moves ? X.len[g] : X.max_moves;
-    for (uint32_t j = 0; j < len; ++j) {
-        const size_t e = (size_t)j * X.G + g;
-        uint8_t fin; const float z = example_outcome(flags, (X.info[e] >> 16) & 0xFFu, fin);
-        X.z[e] = z; X.fin[e] = fin;
-    }
+    examples_settle(X, g, open_from[g], flags);
 }
 
 // Minibatch rows (tafl_examples_gather): row i = example index[i] under symmetry sym[i].  The dense policy row (4 * action_size bytes, at
@@ -78,7 +74,8 @@ int tafl_examples_create(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint
     x->ctx = c; x->n_games = n_games; x->max_moves = max_moves; x->max_children = max_children;
     const size_t E = (size_t)n_games * max_moves, BW = ((size_t)c->n * c->n + 3) / 4;
     if (x->need(x->len, 4 * (size_t)n_games) || x->need(x->boards, 4 * E * BW) || x->need(x->info, 4 * E) || x->need(x->played, 4 * E) || x->need(x->move_no, 4 * E) ||
-        x->need(x->pol, 4 * E * max_children) || x->need(x->z, 4 * E) || x->need(x->fin, E) || x->need(x->counters, 8 * EX_COUNTERS)) {
+        x->need(x->pol, 4 * E * max_children) || x->need(x->z, 4 * E) || x->need(x->fin, E) || x->need(x->counters, 8 * EX_COUNTERS) ||
+        x->need(x->open_from, 4 * (size_t)n_games)) {
         tafl_examples_destroy(x);
         return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_examples_create)");
     }
@@ -104,6 +101,7 @@ int tafl_examples_clear(tafl_examples* x) {
     hipStream_t s = x->ctx->stream;
     HIPCHK(hipMemsetAsync(x->len.p, 0, 4 * (size_t)x->n_games, s));
     HIPCHK(hipMemsetAsync(x->counters.p, 0, 8 * EX_COUNTERS, s));
+    HIPCHK(hipMemsetAsync(x->open_from.p, 0, 4 * (size_t)x->n_games, s));
     return sync_ok(x->ctx);
 }
 int tafl_examples_counts(tafl_examples* x, uint32_t* out_len, uint64_t* out_total) {
@@ -155,7 +153,7 @@ int tafl_examples_finalize(tafl_examples* x, tafl_batch* b) {
     if (const int rc = join_search(b)) return rc;
     tafl_ctx* c = b->ctx;
     if (c != x->ctx) HIPCHK(hipStreamSynchronize(x->ctx->stream));
-    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_examples_finalize<t.NL>), c, b->n, b->soa, x->mem); });
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_examples_finalize<t.NL>), c, b->n, b->soa, x->mem, x->open_from.as<const uint32_t>()); });
     HIPCHK(hipGetLastError());
     return sync_ok(c);
 }

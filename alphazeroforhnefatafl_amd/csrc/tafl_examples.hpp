@@ -130,6 +130,17 @@ static TAFL_HD float example_outcome(uint32_t flags, uint32_t side, uint8_t& fin
     return status == TAFL_STATUS_DRAW ? (float)TAFL_DRAW_VALUE : 0.0f;
 }
 
+// z and the final mark of the examples `from` .. len[g] of game g from the flags word of the position their game stands at (the rule of
+// tafl_examples_finalize; an episodes run settles the examples of an episode that has just ended with it)
+static TAFL_HD void examples_settle(const ExamplesMem& X, uint32_t g, uint32_t from, uint32_t flags) {
+    const uint32_t len = X.len[g] < X.max_moves ? X.len[g] : X.max_moves;
+    for (uint32_t j = from; j < len; ++j) {
+        const size_t e = (size_t)j * X.G + g;
+        uint8_t fin; const float z = example_outcome(flags, (X.info[e] >> 16) & 0xFFu, fin);
+        X.z[e] = z; X.fin[e] = fin;
+    }
+}
+
 // the word (sample_seed, global game id, move number in the episode) draws the play of a move with: independent of the sharding
 static TAFL_HD uint32_t selfplay_rand(uint64_t sample_seed, uint64_t game_id, uint32_t move_no) {
     using E = Engine<2, 7>;

@@ -177,6 +177,35 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_step(Consts<NL> C, Gui
     Guided<NL, W>::selfplay_step(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, rec, C, gs, nz);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+// the round of an episodes run (tafl_gselfplay_begin_episodes), without and with root noise: kernels of their own, so
+// that the ones above stay as they are
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_episodes(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                                   uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::selfplay_step_episodes(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C, gs);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
+template <int NL, int W, bool NOISE>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_episodes(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                                   uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats, RootNoise nz) {
+    static_assert(NOISE, "the noise-free round is k_gselfplay_episodes<NL, W>");
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::selfplay_step_episodes(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C, gs, nz);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
+// close and reopen, right after the round on the same stream: the lanes whose episode ended settle its examples, count it, take their
+// opening and wait with a fresh root (Guided::selfplay_reopen); every other lane leaves at its first load
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_reopen(GuidedMem M, Quad* soa, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    if (Guided<NL, W>::selfplay_reopen(M, g, soa, sp, ep, rec)) atomicAdd(&stats[GS_WAITING], 1ull);
+}
 
 // the arena of a search from fresh roots: max_sims + 1 nodes and (max_sims + 1) x edges_per_node edges per game; the guided stats are zeroed
 static int gmcts_arena(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, const char* name) {
@@ -433,14 +462,21 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st, b->g_noise); });
+    if (b->gsp_episodes) {
+        if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_episodes<t.NL, t.W, true>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise); });
+        else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_episodes<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+        HIPCHK(hipGetLastError());
+        dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+    }
+    else if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st, b->g_noise); });
     else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_step<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_rec, st); });
     HIPCHK(hipGetLastError());
     return TAFL_OK;
 }
 
-int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
-                         tafl_examples* ex) {
+// tafl_gselfplay_begin, and with `eo` tafl_gselfplay_begin_episodes (`openings` then names the batch whose states are the openings)
+static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
+                           tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings) {
     if (!b || !o || n_sims == 0 || edges_per_node == 0 || n_moves == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: bad argument");
     if (n_sims > 0xFFFFu) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: n_sims must be below 65536 (Nsa is stored in 16 bits)");
     if (o->flags != 0 || o->_reserved[0] != 0 || o->_reserved[1] != 0 || o->_reserved[2] != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_opts: flags and reserved words must be 0");
@@ -448,14 +484,39 @@ int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node
     if (ex && (ex->n_games != b->n || ex->ctx->device != b->ctx->device || ex->ctx->n != b->ctx->n))
         return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: the examples object was created for another batch size, board or device");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
-    b->gsp_active = false;
+    if (eo) {
+        if (eo->flags != 0 || eo->_reserved[0] != 0 || eo->_reserved[1] != 0 || eo->_reserved[2] != 0 || eo->_reserved[3] != 0)
+            return fail(TAFL_ERR_UNSUPPORTED, "tafl_episode_opts: flags and reserved words must be 0");
+        if (o->move_base != 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin_episodes: move_base must be 0 (move numbers are per episode)");
+        if (openings->n != n || openings->ctx->device != c->device || openings->ctx->n != c->n || openings->ctx->nl != c->nl)
+            return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin_episodes: the openings batch has another size, board or device");
+    }
+    b->gsp_active = false; b->gsp_has = false;                 // (a begin that fails from here on leaves no run to step, end or ask for stats)
     if (const int rc = join_search(b)) return rc;
+    if (eo && openings != b) {
+        if (const int rc = join_search(openings)) return rc;
+        if (openings->ctx != c) { HIPCHK(hipSetDevice(openings->ctx->device)); HIPCHK(hipStreamSynchronize(openings->ctx->stream)); }
+    }
     if (ex) { HIPCHK(hipSetDevice(ex->ctx->device)); HIPCHK(hipStreamSynchronize(ex->ctx->stream)); }      // (clears and gathers of another context's stream)
     HIPCHK(hipSetDevice(c->device));
     b->tree_live = false; b->g_tree_live = false; b->ran = false;      // the run plays away from the roots of both retained trees
     if (const int rc = gmcts_arena(b, n_sims, edges_per_node, "tafl_gselfplay_begin")) return rc;
     NEED(b->gsp_moves_done, sizeof(uint32_t) * (size_t)n); NEED(b->gsp_plays, sizeof(tafl_play) * (size_t)n * n_moves);
     b->gsp_moves_done.bind(b->gsp.moves_done); b->gsp_plays.bind(b->gsp.plays); b->gsp.n_moves = n_moves;
+    b->gsp_episodes = eo != nullptr; b->gsp_ep = GEpisodes{};
+    if (eo) {
+        const size_t state_bytes = sizeof(Quad) * (size_t)quads_of(c) * n;
+        NEED(b->gsp_episode, sizeof(uint32_t) * (size_t)n); NEED(b->gsp_ep_start, sizeof(uint32_t) * (size_t)n); NEED(b->gsp_openings, state_bytes);
+        NEED(b->gsp_ep_counters, sizeof(unsigned long long) * EP_COUNT);
+        GEpisodes& ep = b->gsp_ep;
+        b->gsp_episode.bind(ep.episode); b->gsp_ep_start.bind(ep.ep_start); b->gsp_ep_counters.bind(ep.ep_counters);
+        ep.openings = b->gsp_openings.as<const Quad>(); ep.open_from = ex ? ex->open_from.as<uint32_t>() : nullptr;
+        ep.episode_moves = eo->episode_moves; ep.id_stride = eo->id_stride ? eo->id_stride : (uint64_t)n;
+        HIPCHK(hipMemsetAsync(b->gsp_episode.p, 0, sizeof(uint32_t) * (size_t)n, c->stream));
+        HIPCHK(hipMemsetAsync(b->gsp_ep_start.p, 0, sizeof(uint32_t) * (size_t)n, c->stream));
+        HIPCHK(hipMemsetAsync(b->gsp_ep_counters.p, 0, sizeof(unsigned long long) * EP_COUNT, c->stream));
+        HIPCHK(hipMemcpyAsync(b->gsp_openings.p, openings->soa, state_bytes, hipMemcpyDeviceToDevice, c->stream));      // the copy the run reopens from
+    }
     b->gsp_rec = SelfPlayRec{};
     if (ex) b->gsp_rec.ex = ex->mem;
     b->gsp_rec.sample_seed = o->sample_seed; b->gsp_rec.game_id_base = game_id_base; b->gsp_rec.temp_moves = o->temp_moves; b->gsp_rec.move_base = o->move_base;
@@ -468,6 +529,30 @@ int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node
     b->g_has = true; b->g_max_sims = n_sims;
     if (const int rc = gselfplay_launch(b, nullptr, nullptr)) return rc;      // the first round: every live root waits for its evaluation
     b->gsp_has = true; b->gsp_active = true; b->gsp_first = true;
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
+                         tafl_examples* ex) {
+    return gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, nullptr, nullptr);
+}
+
+int tafl_gselfplay_begin_episodes(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
+                                  tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings) {
+    if (!b || !eo) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin_episodes: bad argument");
+    return gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b);
+}
+
+int tafl_gselfplay_episode_stats(tafl_batch* b, uint32_t* out_episodes, tafl_episode_stats* out) {
+    if (!b || !b->gsp_has || !b->gsp_episodes || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_episode_stats: tafl_gselfplay_begin_episodes first");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[EP_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->gsp_ep_counters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    COPY_OUT(out_episodes, b->gsp_episode.p, b->n, c->stream);
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memset(out, 0, sizeof *out);
+    out->attacker_wins = h[EP_ATTACKER]; out->defender_wins = h[EP_DEFENDER]; out->draws = h[EP_DRAW]; out->cut = h[EP_CUT];
     return TAFL_OK;
 }
 
@@ -490,7 +575,7 @@ int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves)
     COPY_OUT(out_plays, b->gsp_plays.p, (size_t)n * b->gsp.n_moves, c->stream);
     COPY_OUT(out_moves, b->gsp_moves_done.p, n, c->stream);
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (out_moves) for (uint32_t g = 0; g < n; ++g) out_moves[g] &= ~kGspStopped;
+    if (out_moves) for (uint32_t g = 0; g < n; ++g) out_moves[g] &= ~(kGspStopped | kGspEpisodeEnded);
     return TAFL_OK;
 }
 

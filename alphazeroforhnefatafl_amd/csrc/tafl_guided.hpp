@@ -56,10 +56,22 @@ struct GuidedMem {
 struct GuidedStats { uint32_t sims, predicts, terminal_hits, faults, depth; };
 // per-run state of a guided self-play run (tafl_gselfplay_*)
 constexpr uint32_t kGspStopped = 0x80000000u;    // GSelfPlay::moves_done: the game makes no further move in this run
+constexpr uint32_t kGspEpisodeEnded = 0x40000000u;   // episodes run: the lane's episode is over or cut, k_gselfplay_reopen closes it and opens the next
+enum { EP_ATTACKER = 0, EP_DEFENDER, EP_DRAW, EP_CUT, EP_COUNT };
 struct GSelfPlay {
     uint32_t* moves_done;        // [G] moves made in this run | kGspStopped
     tafl_play* plays;            // [m * G + g] the play of move m (all-zero: not made)
     uint32_t n_moves;
+};
+// what an episodes run (tafl_gselfplay_begin_episodes) adds to it: an argument of the episodes kernels alone
+struct GEpisodes {
+    uint32_t episode_moves;      // an episode that has made this many moves and is still going is cut (0: no cap)
+    uint32_t* episode;           // [G] k: episodes of the lane that are closed or cut = the number of the one that is open
+    uint32_t* ep_start;          // [G] moves the lane had made when its open episode began
+    const Quad* openings;        // quad-plane SoA [QUADS][G]: the position every episode of lane g begins from
+    unsigned long long* ep_counters;   // [EP_COUNT]
+    uint64_t id_stride;          // game id of episode k of lane g = game_id_base + k * id_stride + g
+    uint32_t* open_from;         // [G] of the examples object (null: nothing is recorded): first example of the lane's open episode
 };
 // Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
 struct RootNoise {
@@ -396,21 +408,39 @@ struct Guided {
     // (= do_valid_play) when the edge was first visited.  A game that faults, is over, has no visited root edge or has made n_moves moves stops.
     static TAFL_HD void selfplay_step(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                       const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs) {
-        selfplay_step_as<false>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, nullptr);
+        selfplay_step_as<false, false>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, nullptr, nullptr);
     }
     // the round with root noise: alpha, epsilon and seed of `nz`; gid and M are the run's (rec.game_id_base + g, rec.move_base + moves made)
     static TAFL_HD void selfplay_step(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                       const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz) {
-        selfplay_step_as<true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, &nz);
+        selfplay_step_as<true, false>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, &nz, nullptr);
     }
-    template <bool NOISE>
+    // the round of an episodes run (tafl_gselfplay_begin_episodes), without and with root noise: gid and M are those of the lane's open
+    // episode, and a game that ends (or an episode that reaches its cap) with budget left marks the lane kGspEpisodeEnded instead of
+    // stopping it; selfplay_reopen does the rest
+    static TAFL_HD void selfplay_step_episodes(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                               const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs) {
+        selfplay_step_as<false, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, nullptr, &ep);
+    }
+    static TAFL_HD void selfplay_step_episodes(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                               const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz) {
+        selfplay_step_as<true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, &nz, &ep);
+    }
+    template <bool NOISE, bool EPISODES>
     static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                                         const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz) {
+                                         const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep) {
         uint32_t md = sp.moves_done[g];
         if (md & kGspStopped) return;
+        // EPISODES: the game id and the first move of the lane's open episode (rec.move_base is 0); they hold for the whole call, a new
+        // episode begins in selfplay_reopen
+        uint64_t gid = rec.game_id_base + g; uint32_t m0 = 0;
+        if constexpr (EPISODES) {
+            if (md & kGspEpisodeEnded) return;
+            gid += (uint64_t)ep->episode[g] * ep->id_stride; m0 = ep->ep_start[g];
+        }
         // (only the first pass of the loop below expands a leaf, so the move number of the search that is open now serves the whole call)
         RootNoise mine;
-        if constexpr (NOISE) { mine = *nz; mine.gid = rec.game_id_base + g; mine.move_no = rec.move_base + md; }
+        if constexpr (NOISE) { mine = *nz; mine.gid = gid; mine.move_no = EPISODES ? md - m0 : rec.move_base + md; }
         // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
         for (;;) {
             step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr);
@@ -426,8 +456,8 @@ struct Guided {
                     total += v; m += v != 0u;
                 }
             if (m == 0) { sp.moves_done[g] = md | kGspStopped; return; }   // (n_sims == 1: the root was evaluated, no edge visited)
-            const uint32_t move_no = rec.move_base + md;
-            if (move_no < rec.temp_moves) pick = selfplay_pick(eb, h.n_legal, total, selfplay_rand(rec.sample_seed, rec.game_id_base + g, move_no));
+            const uint32_t move_no = EPISODES ? md - m0 : rec.move_base + md;
+            if (move_no < rec.temp_moves) pick = selfplay_pick(eb, h.n_legal, total, selfplay_rand(rec.sample_seed, gid, move_no));
             const GEdge pe = eb[pick];
             S st;
             if (rec.ex.len) {                                                // (tafl_examples.hpp; a guided edge carries its action, unvisited edges lie in between)
@@ -441,11 +471,40 @@ struct Guided {
             Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;
             sp.plays[(size_t)md * M.G + g] = O::to_play(mv);
             md += 1u;
-            if (md >= sp.n_moves || TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { sp.moves_done[g] = md | kGspStopped; return; }
+            if constexpr (EPISODES) {
+                if (md >= sp.n_moves) { sp.moves_done[g] = md | kGspStopped; return; }      // the budget is used up: the episode stays open
+                if (TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING || (ep->episode_moves != 0u && md - m0 >= ep->episode_moves)) { sp.moves_done[g] = md | kGspEpisodeEnded; return; }
+            } else if (md >= sp.n_moves || TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { sp.moves_done[g] = md | kGspStopped; return; }
             sp.moves_done[g] = md;
             init_game(M, g, st);
             priors = nullptr;
         }
+    }
+    // a fresh root that waits for its evaluation: what `step` leaves when it meets the unexpanded root of an ongoing game
+    static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) { init_game(M, g, root); M.kind[g] = 1; }
+    // Close and reopen (include/taflhip.h tafl_gselfplay_begin_episodes) for a lane that selfplay_step_episodes marked kGspEpisodeEnded: the
+    // examples of the episode get their result when its game is over (examples_settle; a cut episode keeps z = 0, final = 0), the
+    // result counters and the lane's episode number go up, the batch state becomes the opening and the new episode's root waits.  A
+    // lane whose opening is over stops.  Returns true when a root now waits.
+    static TAFL_HD bool selfplay_reopen(const GuidedMem& M, uint32_t g, Quad* soa, const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec) {
+        const uint32_t md = sp.moves_done[g];
+        if (!(md & kGspEpisodeEnded) || (md & kGspStopped)) return false;
+        const uint32_t moves = md & ~kGspEpisodeEnded;
+        S st; IO::load_soa(soa, M.G, g, st);
+        const uint32_t status = TAFL_F_STATUS(st.flags);
+        if (rec.ex.len) {
+            if (status != TAFL_STATUS_ONGOING) examples_settle(rec.ex, g, ep.open_from[g], st.flags);
+            ep.open_from[g] = rec.ex.len[g];
+        }
+        const uint32_t what = status == TAFL_STATUS_ONGOING ? (uint32_t)EP_CUT : status == TAFL_STATUS_DRAW ? (uint32_t)EP_DRAW : TAFL_F_WINNER(st.flags) != 0u ? (uint32_t)EP_DEFENDER : (uint32_t)EP_ATTACKER;
+        TAFL_COUNT_ADD(&ep.ep_counters[what], 1);
+        ep.episode[g] += 1u;
+        IO::load_soa(ep.openings, M.G, g, st);
+        if (TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { sp.moves_done[g] = moves | kGspStopped; return false; }
+        IO::store_soa(soa, M.G, g, st);
+        root_waits(M, g, st);
+        ep.ep_start[g] = moves; sp.moves_done[g] = moves;
+        return true;
     }
 };
 

@@ -210,6 +210,10 @@ struct tafl_batch {
     bool gsp_active = false, gsp_first = false, gsp_has = false;
     GSelfPlay gsp = {}; SelfPlayRec gsp_rec = {}; uint32_t gsp_sims = 0; double gsp_cpuct = 0.0;
     DevBuf gsp_moves_done, gsp_plays;
+    // an episodes run (tafl_gselfplay_begin_episodes): per lane the episode number and the move count at which it began, the openings
+    // (quad-plane SoA like the batch states) and the four result counters; gsp_episodes: the run that is open, or was last, is one
+    bool gsp_episodes = false; GEpisodes gsp_ep = {};
+    DevBuf gsp_episode, gsp_ep_start, gsp_openings, gsp_ep_counters;
     // Dirichlet noise at the root (tafl_gmcts_set_root_noise): the setting, and what the open search or run latched at its begin
     bool noise_set = false, g_noise_on = false;
     tafl_root_noise noise_cfg = {}; RootNoise g_noise = {};
@@ -225,6 +229,7 @@ struct tafl_examples {
     uint32_t n_games, max_moves, max_children;
     ExamplesMem mem;
     DevBuf len, boards, info, played, move_no, pol, z, fin, counters;
+    DevBuf open_from;                // [n_games] first example of game g whose result is still open: 0 unless an episodes run has moved it
     DevBuf g_index, g_sym, g_boards, g_sides, g_pi, g_z, g_fin;      // staging of a gather with host pointers
     size_t device_bytes = 0;         // sum of the capacities above: every allocation goes through need()
     int need(DevBuf& d, size_t bytes) { device_bytes -= d.cap; const int rc = d.ensure(bytes); device_bytes += d.cap; return rc; }

@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflExamplesStats, TaflGmctsStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
 
 KC_MOVEGEN, KC_STEP, KC_ROLLOUT, KC_MCTS_TREE, KC_MCTS_ROLLOUT = range(5)
@@ -339,6 +339,26 @@ class GameBatch:
         check(lib().tafl_gselfplay_begin(self._h, n_sims, edges_per_node, c_puct, C.byref(o), n_moves, game_id_base,
                                          examples._h if examples is not None else None))
         self._gsp_moves = n_moves
+
+    def gselfplay_begin_episodes(self, examples: "Examples | None", lane_moves: int, n_sims: int, c_puct: float = 1.0, edges_per_node: int = 256,
+                                 game_id_base: int = 0, sample_seed: int = 0, temp_moves: int = 0, episode_moves: int = 0, id_stride: int = 0,
+                                 openings: "GameBatch | None" = None):
+        """Opens a guided self-play run in episodes (tafl_gselfplay_begin_episodes): gselfplay_begin with `lane_moves` as each lane's move
+        budget over all its games.  A lane whose game ends (or has made `episode_moves` moves, 0: no cap) with budget left gets the
+        result written to that game's examples, takes its opening again - the state of `openings` (None: this batch) at this call -
+        under the game id game_id_base + k * id_stride + lane (id_stride 0: the batch size), and its new root waits in the same round.
+        gselfplay_step, gmcts_leaves and gselfplay_end serve the run as they serve a plain one."""
+        o = TaflSelfplayOpts(sample_seed, temp_moves, 0, 0)
+        eo = TaflEpisodeOpts(id_stride, episode_moves, 0)
+        check(lib().tafl_gselfplay_begin_episodes(self._h, n_sims, edges_per_node, c_puct, C.byref(o), lane_moves, game_id_base,
+                                                  examples._h if examples is not None else None, C.byref(eo), openings._h if openings is not None else None))
+        self._gsp_moves = lane_moves
+
+    def gselfplay_episode_stats(self):
+        """(episodes closed or cut per lane [n], TaflEpisodeStats: attacker_wins, defender_wins, draws, cut) of the episodes run."""
+        eps, st = (C.c_uint32 * self.n)(), TaflEpisodeStats()
+        check(lib().tafl_gselfplay_episode_stats(self._h, eps, C.byref(st)))
+        return eps, st
 
     def gselfplay_step(self, priors=None, values=None, device: bool = False, want_waiting: bool = True) -> int:
         """One round of the run: gmcts_step's arguments (the run's c_puct and n_sims).  Returns the games now waiting; 0: the run is complete."""

@@ -60,3 +60,33 @@ def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     examples.finalize(batch)
     lens, total = examples.counts()
     return lens, total, _games_over(batch)
+
+
+def play_guided_selfplay(batch: GameBatch, examples: Examples, nnet, args: MCTSArgs, lane_moves: int, *, episode_moves: int = 0, openings: GameBatch | None = None,
+                         id_stride: int = 0, game_id_base: int = 0, sample_seed: int = 1, temp_moves: int = 0, edges_per_node: int = 256, device: bool = False,
+                         buffers=None):
+    """Guided self-play in episodes (include/taflhip.h tafl_gselfplay_begin_episodes): every lane of `batch` plays
+    `lane_moves` moves in all, and a lane whose game ends (or reaches `episode_moves` moves, 0: no cap) before that has the result
+    written to the game's examples and begins its next game from its opening - the state of `openings` (None: `batch`) at this call -
+    in the same round, so the evaluator's batch stays full.  Episode k of lane g has the game id game_id_base + k * id_stride + g
+    (id_stride 0: the batch size; a sharded caller passes the total).  The loop is leaves -> network -> step until nothing waits
+    (nnet, device and buffers as in play_guided_episodes); then Examples.finalize settles the open tails.  args.dirichletEpsilon > 0
+    mixes root noise keyed by the episode's game id and move number.  Returns (episodes closed or cut per lane, TaflEpisodeStats,
+    examples recorded in all, (dropped, overflowed))."""
+    apply_root_noise(batch, args)
+    batch.gselfplay_begin_episodes(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
+                                   temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings)
+    waiting = batch.gselfplay_step()
+    while waiting:
+        if device:
+            batch.gmcts_leaves(*buffers)
+            priors, values = nnet.predict_batch(*buffers)
+        else:
+            priors, values = nnet.predict_batch(*batch.gmcts_leaves())
+        waiting = batch.gselfplay_step(priors, values, device=device)
+    batch.gselfplay_end(want_plays=False)
+    episodes, stats = batch.gselfplay_episode_stats()
+    examples.finalize(batch)
+    _lens, total = examples.counts()
+    es = examples.stats()
+    return episodes, stats, total, (es.dropped, es.overflowed)

@@ -430,7 +430,8 @@ int tafl_mcts_policy_device_ex(tafl_batch* b, double temp, uint64_t tie_seed, ui
  * (TAFL_ERR_UNSUPPORTED); opts->flags and the reserved words must be 0 (TAFL_ERR_UNSUPPORTED).  tafl_mcts_get_stats covers all searches.
  *
  * tafl_examples_create: room for max_moves examples per game of n_games games, max_children (1..65535) policy entries each:
- *   n_games * max_moves * (4 * ceil(side_len^2 / 4) + 4 * max_children + 17) bytes on the context's device.  The object outlives runs and
+ *   n_games * max_moves * (4 * ceil(side_len^2 / 4) + 4 * max_children + 17) + 4 * n_games bytes on the context's device (the last term is
+ *   the open_from array of tafl_gselfplay_begin_episodes; tafl_examples_stats.device_bytes counts it for every object).  The object outlives runs and
  *   batches (an episode may be played in several runs, move_base continuing the numbering); destroy it before its context.
  * tafl_examples_clear: every game back to 0 examples, the counters back to 0.
  * tafl_examples_counts: out_len[n_games] (may be NULL) and their sum (may be NULL).  tafl_examples_get_stats: the counters.
@@ -438,6 +439,7 @@ int tafl_mcts_policy_device_ex(tafl_batch* b, double temp, uint64_t tie_seed, ui
  *   it is joined) and writes for every recorded example of that game z as float32 seen from the example's side to move: +1 that side
  *   won, -1 it lost, 1e-4 a draw (the value the search gives a drawn terminal), final = 1; examples of a game that is still going on get
  *   z = 0, final = 0, so the call can be repeated after the next run.
+ *   Examples that an episodes run (tafl_gselfplay_begin_episodes) has closed or cut are left as that run wrote them.
  * tafl_examples_gather: minibatch rows.  For i < count, example index[i] under board symmetry sym[i] in 0..7 (sym == NULL: identity):
  *   boards[i * side_len^2 ..]  the board bytes, transformed;  sides[i], z[i], final_[i] copied;
  *   pi[i * tafl_action_size ..]  float32, zero except pi[sigma(action)] = (float)((double)Nsa / (double)N): the temp = 1 probs of
@@ -557,6 +559,59 @@ int tafl_gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node
                          uint32_t n_moves, uint64_t game_id_base, tafl_examples* ex);
 int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, uint32_t* out_waiting);
 int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves);
+
+/* ---- guided self-play in episodes: a game that ends starts its next game in place ---------------------------------
+ * tafl_gselfplay_begin_episodes opens a tafl_gselfplay run in which a lane does not idle once its game is over: the result is written to
+ * the game's examples on the device, the lane takes its opening again under a new game id, and the new game's root waits for its
+ * evaluation in the same round, so the evaluator's batch stays full.  tafl_gselfplay_step, tafl_gmcts_leaves, tafl_gselfplay_end and
+ * tafl_gmcts_get_stats serve such a run as they serve a plain one.  Build-defined, like the run itself; its expectation is exact: episode k
+ * of lane g equals the plain tafl_gselfplay_begin run from openings[g] with game_id_base + k * id_stride, move_base = 0 and the same seeds
+ * and noise, truncated to the moves the lane had left or to episode_moves.
+ *
+ *   lane budget   n_moves is the lane's move budget over all its episodes; plays[m * n + g] and out_moves of tafl_gselfplay_end keep their
+ *                 meaning (m counts the lane's moves, whichever episode they belong to).
+ *   move numbers  are per episode and start at 0: opts->move_base must be 0 (TAFL_ERR_INVALID_ARG otherwise).
+ *   openings      a batch of the same size, board and device as b (TAFL_ERR_INVALID_ARG otherwise); NULL or b itself: b's states at the
+ *                 call.  Its states are copied into a buffer of b at the call: later writes to either batch do not change them.  Episode 0
+ *                 of a lane begins from b's state, every later one from openings[g].
+ *   episode k     of lane g has gid = game_id_base + k * id_stride + g (id_stride == 0 means n; a sharded caller passes the total number
+ *                 of lanes) and M = the moves that episode has made.  Everything tafl_gselfplay_begin and tafl_root_noise key by (gid, M)
+ *                 uses these: the word that draws a play, temp_moves, the example's move_no, the root-noise key.  The search, the pick,
+ *                 the record and the play are those of tafl_gselfplay_begin, unchanged.
+ *   close, reopen after a play, while the lane has budget left: an episode is CLOSED if its game is over, and CUT if it has made
+ *                 episode_moves moves (0: no cap) and is still going.
+ *                   closed: every example of the episode - indices open_from[g] .. len[g] of the lane's column - gets z by the rule of
+ *                           tafl_examples_finalize from the final position and the example's side to move, and final = 1;
+ *                   cut:    its examples keep z = 0, final = 0.
+ *                 In both cases open_from[g] = len[g], the lane's episode count and one of the four counters of tafl_episode_stats go up,
+ *                 the lane's batch state becomes its opening, k goes up by one, and the fresh root waits for its evaluation in this very
+ *                 round: it is counted in out_waiting and served by tafl_gmcts_leaves.  At most one episode per lane is reopened per step.
+ *                 A lane whose opening is not ongoing stops instead (its batch state stays the finished game).
+ *   stops         a faulted lane, a lane without a visited root edge and a lane whose budget is used up stop as in a plain run.  A lane that
+ *                 stops on its budget leaves its last episode OPEN - also when that game ended on the budget's last move: it is neither
+ *                 counted nor settled by the run, and tafl_examples_finalize(ex, b) treats it as it treats a game of a plain run.
+ *   capacity      `ex` holds max_moves examples per LANE, over all its episodes; dropped and overflowed are counted as before.
+ * tafl_examples_finalize writes only the examples from open_from[g] on.  open_from is zero at tafl_examples_create and after
+ *   tafl_examples_clear and only an episodes run moves it, so for an object that never saw one the call writes what it always wrote.
+ *   tafl_examples_gather, _read and _counts are unchanged; an episode boundary in a lane's column is where move_no returns to 0.
+ * tafl_gselfplay_episode_stats: out_episodes[n] (may be NULL) = the episodes of each lane that were closed or cut, and the counters; valid
+ *   from the begin until the next tafl_gselfplay_begin / _begin_episodes on the batch (TAFL_ERR_INVALID_ARG without an episodes run).
+ * Non-zero eo->flags or reserved words: TAFL_ERR_UNSUPPORTED; eo == NULL: TAFL_ERR_INVALID_ARG; everything tafl_gselfplay_begin rejects is
+ *   rejected alike, and what closes a plain run closes this one.  Not offered: continuing a cut or open episode in a later run. */
+typedef struct tafl_episode_opts {
+    uint64_t id_stride;        /* game id of episode k of lane g = game_id_base + k * id_stride + g; 0 means n */
+    uint32_t episode_moves;    /* an episode that has made this many moves and is still going is cut (0: no cap) */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[4];     /* 0 */
+} tafl_episode_opts;           /* 32 bytes */
+typedef struct tafl_episode_stats {
+    uint64_t attacker_wins, defender_wins, draws;   /* closed episodes by result */
+    uint64_t cut;                                   /* episodes cut at episode_moves */
+    uint64_t _reserved[4];
+} tafl_episode_stats;          /* 64 bytes */
+int tafl_gselfplay_begin_episodes(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* opts,
+                                  uint32_t n_moves, uint64_t game_id_base, tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings);
+int tafl_gselfplay_episode_stats(tafl_batch* b, uint32_t* out_episodes, tafl_episode_stats* out);
 
 /* ---- Dirichlet noise at the root of a guided search --------------------------------------------------------------
  * AlphaZero's root exploration noise, P' = (1 - epsilon) P + epsilon eta with eta ~ Dir(alpha), for tafl_gmcts_* searches from fresh

@@ -14,7 +14,19 @@ wait per round (the evaluator's batch fill) and the step's device time per round
 
 `--noise ALPHA EPS` mixes Dirichlet(ALPHA) noise into every root's priors with weight EPS (tafl_root_noise), seed 1:
 the own-pace run keys it by its own move numbers, the lock-step loop sets the move number before each search, so both still play the
-same games."""
+same games.
+
+`--episodes` measures the run in episodes (tafl_gselfplay_begin_episodes) instead: the lanes start from openings with
+terminal nodes in reach - the start position advanced by random plies spread over 0 .. `--spread` (tafl_random_advance, seed 21) - with a
+lane budget of `--moves` moves (32 in DESIGN.md), and two routes are timed with each evaluator:
+
+  plain      gselfplay_begin with n_moves = the budget: a lane whose game ends idles until the run is over (the parent's route)
+  episodes   gselfplay_begin_episodes with the same budget: a lane whose game ends starts its next game from its opening in place
+
+Both record into an examples object (max_children = S).  Per line also: recorded examples and examples per second, and for the episodes
+route the episodes closed and the result counters.  The per-round cost of k_gselfplay_reopen comes from a trace of its own:
+  rocprofv3 --kernel-trace --stats -d OUT -- python tools/measure_gselfplay.py --episodes --no-conv --runs 1
+(the kernel's row of OUT/*_kernel_stats.csv: total time / calls)."""
 import argparse
 import ctypes as C
 import json
@@ -34,6 +46,8 @@ def main():
     ap.add_argument("--channels", type=int, default=32)
     ap.add_argument("--runs", type=int, default=3)
     ap.add_argument("--no-conv", action="store_true", help="only the constant-prior evaluator")
+    ap.add_argument("--episodes", action="store_true", help="the run in episodes against the plain run, from openings spread over the game (DESIGN.md section 15)")
+    ap.add_argument("--spread", type=int, default=500, help="--episodes: lane g starts from the start position advanced by (7 g) mod SPREAD random plies")
     ap.add_argument("--noise", type=float, nargs=2, metavar=("ALPHA", "EPS"), help="Dirichlet noise at every root (default: off)")
     args = ap.parse_args()
     import numpy as np
@@ -144,7 +158,63 @@ def main():
             b.do_play(plays_of(visits.argmax(1)), want_effects=True)
         return sims
 
+    def fill(b, net, r, begin):
+        """the step loop of a recording run opened by `begin`; returns the evaluated simulations"""
+        noise(b)
+        begin()
+        w = b.gselfplay_step()
+        while w:
+            r.rounds += 1; r.waiting += w
+            b.gmcts_leaves(*bufs)
+            p, v = net.predict_batch()
+            w = r.timed(lambda: b.gselfplay_step(p, v, device=True))
+        b.gselfplay_end(want_plays=False)
+        return b.gmcts_stats().sims
+
     nets = [("constant_priors", Const())] + ([] if args.no_conv else [("torch_conv_fp16", Conv())])
+    if args.episodes:
+        plies = (C.c_uint32 * n)(*[(7 * g) % args.spread for g in range(n)])
+        start = lg.new_batch(n, boards.COPENHAGEN)
+        start.random_advance(21, plies, 0)
+        openings = start.download()
+        over0 = int(np.count_nonzero(np.frombuffer(openings, np.uint8).reshape(n, C.sizeof(abi.TaflState))[:, abi.TaflState.status.offset]))
+        start.close()
+        ex = lg.new_examples(n, moves, S)
+        for name, net in nets:
+            for _ in range(3):
+                net.predict_batch()
+            for route in ("plain", "episodes"):
+                b = lg.new_batch(n)
+                secs, last = [], None
+                for i in range(1 + args.runs):
+                    b.upload(openings)
+                    ex.clear()
+                    bt.zero_(); st.zero_(); wt.zero_()
+                    r = Rounds()
+                    begin = (lambda: b.gselfplay_begin(ex, moves, S, 1.0, epn, sample_seed=1)) if route == "plain" else \
+                            (lambda: b.gselfplay_begin_episodes(ex, moves, S, 1.0, epn, sample_seed=1))
+                    lg.sync(); torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    sims = fill(b, net, r, begin)
+                    lg.sync(); torch.cuda.synchronize()
+                    dt = time.perf_counter() - t0
+                    if i:
+                        secs.append(dt)
+                    last = (sims, r, r.step_ms())
+                sims, r, ms = last
+                total = ex.counts()[1]
+                es = ex.stats()
+                line = {"evaluator": name, "route": route, "lanes": n, "lanes_over_at_the_start": over0, "spread": args.spread, "sims_per_move": S, "lane_budget": moves,
+                        "edges_per_node": epn, "noise": args.noise, "seconds_min": round(min(secs), 3), "seconds_max": round(max(secs), 3), "sims": sims,
+                        "sims_per_sec_best": sims / min(secs), "sims_per_sec_worst": sims / max(secs), "examples": total,
+                        "examples_per_sec_best": total / min(secs), "examples_per_sec_worst": total / max(secs), "dropped": es.dropped, "overflowed": es.overflowed,
+                        "rounds": r.rounds, "mean_fraction_waiting": r.waiting / max(1, r.rounds) / n, "step_ms_per_round": ms / max(1, r.rounds), "step_ms_total": ms}
+                if route == "episodes":
+                    eps, est = b.gselfplay_episode_stats()
+                    line.update({"episodes_closed_or_cut": int(sum(eps)), "attacker_wins": est.attacker_wins, "defender_wins": est.defender_wins, "draws": est.draws, "cut": est.cut})
+                print(json.dumps(line), flush=True)
+                b.close()
+        return
     final = {}
     for name, net in nets:
         for _ in range(3):
