@@ -185,11 +185,12 @@ template <int NLS, int WS, int NL, int W, int PRESET>
 __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK) void k_rollout(Consts<NL> Carg, const Quad* soa, uint32_t n, uint64_t seed, uint32_t sim, uint32_t max_plies,
                                                         uint64_t base, tafl_rollout_result* out) {
     const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
-    if (g >= n) return;
     TAFL_PICK_CONSTS(C, Carg);
+    const auto lut = playout_tables<NL, W, PRESET>();            // filled by the whole workgroup: before any lane leaves
+    if (g >= n) return;
     DState<NL> st; load_batch_state<NLS, WS, NL, W>(soa, n, g, C.n, st);
     tafl_rollout_result r;
-    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r);
+    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut);
     out[g] = r;
 }
 

@@ -18,6 +18,7 @@
 #pragma once
 #include "tafl_bits.hpp"
 #include "../../include/taflhip.h"
+#include "tafl_tables.hpp"
 
 namespace tafl {
 
@@ -590,8 +591,10 @@ struct Engine {
     static TAFL_HD void apply_pre(S& st, const Move& m, const K& C, ApplyCtx& ax) { apply_pre(st, m, C, ax, st.flags & TAFL_F_SIDE); }
     // the same with the mover handed in: `mover` must equal st.flags & TAFL_F_SIDE.  The playout loop of tafl_fast.hpp passes a
     // compile-time constant (its two half-iterations each serve one side), which folds every `mover ? a : b` below and in captures().
-    static TAFL_HD void apply_pre(S& st, const Move& m, const K& C, ApplyCtx& ax, const uint32_t mover) {
-        const B fbit = bit_at<NL>(m.from), tbit = bit_at<NL>(m.to);
+    // lut: how a run-time tile index becomes its one-bit mask (tafl_tables.hpp); the default is the computed bit_at
+    template <class L = IdxComputed<NL>>
+    static TAFL_HD void apply_pre(S& st, const Move& m, const K& C, ApplyCtx& ax, const uint32_t mover, const L& lut = L()) {
+        const B fbit = lut.bit(m.from), tbit = lut.bit(m.to);
         const bool mover_is_king = mover && m.from == king_sq(st, C);
         // board.move_piece (board/state.rs:218-223): clear `from`, set `to` on the mover's side — branch-free
         {

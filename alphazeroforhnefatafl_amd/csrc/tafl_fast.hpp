@@ -248,8 +248,8 @@ struct Fast {
     // attacker's play, the king-escape and exit-fort tests only behind a defender's, the king-capture block only in the attacker's half.
     // 64 games share an instruction stream: before, a wave paid for both sides' code on every ply.
     // g: plays of MOVER on entry, of the other side on exit; rk: the ply's RNG word before mixing (sk + ply * 0x85EBCA77, kept incrementally).
-    template <uint32_t MOVER>
-    static TAFL_HD void ply_of(S& st, B& attT, B& defT, Gen& g, uint32_t& rk, const K& C, const F& fc) {
+    template <uint32_t MOVER, class L = IdxComputed<NL>>
+    static TAFL_HD void ply_of(S& st, B& attT, B& defT, Gen& g, uint32_t& rk, const K& C, const F& fc, const L& lut = L()) {
         TAFL_PROF_COUNT(31); TAFL_STAT_HIT(31);
         TAFL_PROF_BEGIN(10); TAFL_PROF_SPLIT(10); TAFL_PROF_END(11);      // two empty sections: the cost of a mark
         TAFL_PROF_BEGIN(0);
@@ -258,14 +258,14 @@ struct Fast {
         const Move m = pick(st, attT, defT, g, idx, C);
         TAFL_PROF_SPLIT(0);
         typename E::ApplyCtx ax;
-        E::apply_pre(st, m, C, ax, MOVER);
+        E::apply_pre(st, m, C, ax, MOVER, lut);
         TAFL_PROF_SPLIT(4);
         // T layout upkeep: the move, the custodial captures (V+- are +-1 here, H+- are +-W), then whatever else was
         // captured (shieldwall, king, Linnaean: rare)
         {
             constexpr int BK = 2 * W;
             const uint32_t tT = n_to_t(m.to);
-            const B mvT = bit_at<NL>(n_to_t(m.from)) | bit_at<NL>(tT);
+            const B mvT = lut.bit(n_to_t(m.from)) | lut.bit(tT);
             if constexpr (MOVER != 0) defT = defT ^ mvT; else attT = attT ^ mvT;
             const uint32_t cu = ax.cust;
             const uint64_t cf = ((uint64_t)(cu & 1u) << (BK + 1)) | ((uint64_t)((cu >> 1) & 1u) << (BK - 1))
@@ -292,7 +292,8 @@ struct Fast {
     }
 
     // one seeded uniform-random playout; identical results to Engine::rollout
-    static TAFL_HD void rollout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& res) {
+    template <class L = IdxComputed<NL>>
+    static TAFL_HD void rollout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& res, const L& lut = L()) {
         const F fc = make_fast_consts<NL>(C);
         const uint32_t start_side = st.flags & TAFL_F_SIDE;
         B attT, defT;
@@ -310,9 +311,9 @@ struct Fast {
         bool active = goes_on();
         bool skip_first = start_side != 0;     // a playout that starts with a defender's play sits out the first (attacker's) half
         while (wave_any(active)) {
-            if (active && !skip_first) { ply_of<0>(st, attT, defT, g, rk, C, fc); ++ply; active = goes_on(); }
+            if (active && !skip_first) { ply_of<0>(st, attT, defT, g, rk, C, fc, lut); ++ply; active = goes_on(); }
             skip_first = false;
-            if (active) { ply_of<1>(st, attT, defT, g, rk, C, fc); ++ply; active = goes_on(); }
+            if (active) { ply_of<1>(st, attT, defT, g, rk, C, fc, lut); ++ply; active = goes_on(); }
         }
         E::finish_rollout(st, start_side, ply, stuck, res);
     }

@@ -55,6 +55,22 @@ static_assert(TAFL_MCTS_MAX_SLOTS == tafl::kMctsMaxSlots, "slot bound of tafl_op
     constexpr Consts<NL> C##_ct = preset_consts<NL, W, PRESET>();                   \
     const Consts<NL>& C = (PRESET != PRESET_NONE) ? C##_ct : (Carg)
 
+// The index policy of a playout kernel (tafl_tables.hpp): the bit_at table in LDS, filled by the whole workgroup, for the preset kernels
+// of the layouts that keep one; the computed code for every other instantiation (run-time rules, dense 13x13).  Call it before any lane
+// of the workgroup leaves the kernel.
+template <int NL, int W, int PRESET>
+__device__ __forceinline__ auto playout_tables() {
+    if constexpr (PRESET == PRESET_NONE || !playout_bit_table<NL>()) return IdxComputed<NL>();
+    else {
+        using L = IdxTables<NL>;
+        __shared__ typename L::Row mem[L::ROWS];
+        L::fill(mem, threadIdx.x, blockDim.x);
+        __syncthreads();
+        L lut; lut.base = mem;
+        return lut;
+    }
+}
+
 // game g of the batch (quad-plane SoA in the reference layout <NLS, WS>) in the layout <NL, W> the kernel works in: the same, or the dense
 // 13-column layout of the 13x13 preset (restride, tafl_core.hpp)
 template <int NLS, int WS, int NL, int W>

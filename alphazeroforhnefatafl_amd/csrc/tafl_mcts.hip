@@ -165,12 +165,13 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK, TAFL_ROLLOUT_WAVES) void k_m
     if (blockIdx.x * TAFL_BLOCK >= cnt) return;
     const uint32_t i = blockIdx.x * TAFL_BLOCK + threadIdx.x;
     TAFL_PICK_CONSTS(C, Carg);
+    const auto lut = playout_tables<NL, W, PRESET>();            // (every lane of the workgroup is still here)
     const bool has = i < cnt;
     uint32_t cls = 0, off = 0;
     TAFL_UNROLL for (uint32_t t = 1; t < TAFL_MCTS_MAX_SLOTS; ++t) { const bool ge = i >= pre[t]; cls = ge ? t : cls; off = ge ? pre[t] : off; }
     const uint32_t e = has ? work[(size_t)cls * stride + (i - off)] : 0u;
     const uint32_t j = e >> 27, g = e & 0x07FFFFFFu;
-    if (has) Ops<NL, W>::mcts_slot_rollout(M, j, g, seed, base + g, sim_offset, max_plies, C);
+    if (has) Ops<NL, W>::mcts_slot_rollout(M, j, g, seed, base + g, sim_offset, max_plies, C, lut);
     if ((threadIdx.x & 63) == 0) atomicAdd(&stats[ST_EXEC], (unsigned long long)__popcll(__ballot(has)));
 }
 
@@ -188,6 +189,7 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK, TAFL_ROLLOUT_WAVES) void k_m
     const uint32_t tg = blockIdx.x * GPW + lane;                  // tree phase: lane < GPW serves game tg
     const uint32_t rj = lane / GPW, rg = blockIdx.x * GPW + (lane % GPW);   // playout phase: slot rj of game rg
     TAFL_PICK_CONSTS(C, Carg);
+    const auto lut = playout_tables<NL, W, PRESET>();
     LaneStats ls; ls.sims = ls.rollouts = ls.rollout_plies = ls.depth = ls.scanned = ls.terminal_hits = ls.faults = ls.reason = 0;
     ls.reason_hist4 = 0; ls.spec_issued = ls.spec_hits = 0;
     uint32_t executed = 0, finished = 0;
@@ -206,7 +208,7 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK, TAFL_ROLLOUT_WAVES) void k_m
         const bool work = rg < M.G && rj < M.spec_k && M.spec_kind[(size_t)rj * M.G + rg] == 1;
         const unsigned long long wb = __ballot(work);
         if (wb == 0ull) continue;
-        if (work) Ops<NL, W>::mcts_slot_rollout(M, rj, rg, seed, base + rg, sim_offset, max_plies, C);
+        if (work) Ops<NL, W>::mcts_slot_rollout(M, rj, rg, seed, base + rg, sim_offset, max_plies, C, lut);
         executed += (uint32_t)__popcll(wb);
         __threadfence();
     }

@@ -7,6 +7,8 @@
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -ffp-contract=off -I alphazeroforhnefatafl_amd/csrc [-DLB=4] [-DVARIANT=..] \
 //         -mllvm --amdgpu-sched-strategy=max-ilp -o /tmp/rollout_bench tools/rollout_bench.hip
 //   /tmp/rollout_bench [board: 11|13|7] [max_plies=512] [reps=3]
+// -DLUT: bit_at from the LDS table of tafl_tables.hpp (boards 11 and 7), as in the product's preset playout kernels; without it the
+// computed code.  -DDENSE13: board 13 in the dense 13-column layout <6, 13> the product's 13x13 playout kernels work in.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -30,15 +32,32 @@ static const char* const PROF_NAME[12] = {"pick", "captures: custodial fields", 
                                           "gen (next mover's four reach sets)", "outcome + finish", "  of which enclosure flood", "  of which exit fort", "empty mark", "empty mark"};
 #endif
 
-template <int NL, int W, int PRESET>
+template <int NL>
+__device__ __forceinline__ auto bench_tables() {
+#ifdef LUT
+    if constexpr (playout_bit_table<NL>()) {
+        using L = IdxTables<NL>;
+        __shared__ typename L::Row mem[L::ROWS];
+        L::fill(mem, threadIdx.x, 64u);
+        __syncthreads();
+        L lut; lut.base = mem;
+        return lut;
+    } else
+#endif
+    return IdxComputed<NL>();
+}
+template <int NLS, int WS, int NL, int W, int PRESET>
 __global__ __launch_bounds__(64, LB) void k_roll(const Quad* soa, uint32_t n, uint64_t seed, uint32_t sim, uint32_t max_plies, uint64_t base,
                                                  tafl_rollout_result* out) {
     const uint32_t g = blockIdx.x * 64 + threadIdx.x;
-    if (g >= n) return;                                  // (-DEXTRA_GRID=k launches k x the blocks needed: the surplus leaves here)
     constexpr Consts<NL> C = preset_consts<NL, W, PRESET>();
-    DState<NL> st; StateIO<NL>::load_soa(soa, n, g, st);
+    const auto lut = bench_tables<NL>();
+    if (g >= n) return;                                  // (-DEXTRA_GRID=k launches k x the blocks needed: the surplus leaves here)
+    DState<NL> st;
+    if constexpr (NLS == NL && WS == W) StateIO<NL>::load_soa(soa, n, g, st);
+    else { DState<NLS> t; StateIO<NLS>::load_soa(soa, n, g, t); restride<NLS, WS, NL, W>(t, C.n, st); }
     tafl_rollout_result r;
-    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r);
+    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut);
     out[g] = r;
 }
 template <int NL>
@@ -49,7 +68,7 @@ __global__ void k_fill(Quad* soa, uint32_t n, DState<NL> st) {
 
 #define CK(e) do { hipError_t e_ = (e); if (e_ != hipSuccess) { fprintf(stderr, "%s: %s\n", #e, hipGetErrorString(e_)); return 1; } } while (0)
 
-template <int NL, int W, int PRESET>
+template <int NL, int W, int PRESET, int NLK = NL, int WK = W>
 int run(const char* board, uint32_t word_bits, uint32_t max_plies, int reps) {
     tafl_state st; std::string err;
     if (fen_to_state(preset_board(board), 0, word_bits, &st, &err)) { fprintf(stderr, "fen: %s\n", err.c_str()); return 1; }
@@ -63,7 +82,7 @@ int run(const char* board, uint32_t word_bits, uint32_t max_plies, int reps) {
         float best = 1e30f;
         for (int r = 0; r < reps + 1; ++r) {
             CK(hipEventRecord(a, 0));
-            hipLaunchKernelGGL((k_roll<NL, W, PRESET>), dim3(n / 64 * EXTRA_GRID), dim3(64), 0, 0, soa, n, 3ull, 0u, max_plies, 0ull, out);
+            hipLaunchKernelGGL((k_roll<NL, W, NLK, WK, PRESET>), dim3(n / 64 * EXTRA_GRID), dim3(64), 0, 0, soa, n, 3ull, 0u, max_plies, 0ull, out);
             CK(hipEventRecord(b, 0)); CK(hipDeviceSynchronize());
             float ms; CK(hipEventElapsedTime(&ms, a, b));
             if (r > 0 && ms < best) best = ms;
@@ -103,7 +122,11 @@ int main(int argc, char** argv) {
     const uint32_t max_plies = argc > 2 ? (uint32_t)atoi(argv[2]) : 512u;
     const int reps = argc > 3 ? atoi(argv[3]) : 3;
     if (board == 11) return run<4, 11, PRESET_COPENHAGEN11>("copenhagen", 128, max_plies, reps);
+#ifdef DENSE13
+    if (board == 13) return run<8, 15, PRESET_COPENHAGEN13, 6, 13>("copenhagen13", 256, max_plies, reps);
+#else
     if (board == 13) return run<8, 15, PRESET_COPENHAGEN13>("copenhagen13", 256, max_plies, reps);
+#endif
     if (board == 7) return run<2, 7, PRESET_BRANDUBH7>("brandubh", 64, max_plies, reps);
     fprintf(stderr, "board must be 7, 11 or 13\n");
     return 2;
