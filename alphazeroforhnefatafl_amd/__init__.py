@@ -7,7 +7,7 @@ from . import abi
 from .abi import Ruleset, boards, rules
 
 __all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples",
-           "play_episodes", "play_guided_episodes", "play_guided_selfplay"]
+           "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult"]
 
 
 def __getattr__(name):
@@ -18,7 +18,7 @@ def __getattr__(name):
     if name in ("MCTS", "MCTSArgs", "GuidedMCTS"):
         from . import mcts
         return getattr(mcts, name)
-    if name in ("play_episodes", "play_guided_episodes", "play_guided_selfplay"):
+    if name in ("play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult"):
         from . import selfplay
         return getattr(selfplay, name)
     if name == "BatchedGame":

@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -85,6 +85,10 @@ SYMBOLS = [
     ("tafl_gselfplay_end", _i32, [_vp, _P(TaflPlay), _P(_u32)]),
     ("tafl_gselfplay_begin_episodes", _i32, [_vp, _u32, _u32, _dbl, _P(TaflSelfplayOpts), _u32, _u64, _vp, _P(TaflEpisodeOpts), _vp]),
     ("tafl_gselfplay_episode_stats", _i32, [_vp, _P(_u32), _P(TaflEpisodeStats)]),
+    ("tafl_gmatch_begin", _i32, [_vp, _u32, _u32, _dbl, _P(TaflSelfplayOpts), _u32, _u64, _vp, _P(TaflEpisodeOpts), _vp, _P(TaflMatchOpts)]),
+    ("tafl_gmatch_leaves", _i32, [_vp, _P(TaflMatchIo), _i32, _P(_u32)]),
+    ("tafl_gmatch_step", _i32, [_vp, _P(_vp), _P(_vp), _i32]),
+    ("tafl_gmatch_get_stats", _i32, [_vp, _P(TaflMatchStats)]),
     ("tafl_gmcts_set_root_noise", _i32, [_vp, _P(TaflRootNoise)]),
     ("tafl_root_noise_eval", _i32, [_vp, _P(TaflRootNoise), _vp, _i32]),
     ("tafl_gmcts_root_priors", _i32, [_vp, _vp, _i32]),

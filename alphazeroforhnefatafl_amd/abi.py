@@ -175,6 +175,22 @@ class TaflEpisodeStats(C.Structure):
                 ("_reserved", C.c_uint64 * 4)]
 
 
+class TaflMatchOpts(C.Structure):
+    """tafl_match_opts: a match run (tafl_gmatch_begin); swap 0 or 1 chooses which evaluator takes the attackers first."""
+    _fields_ = [("swap", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 6)]
+
+
+class TaflMatchIo(C.Structure):
+    """tafl_match_io: where tafl_gmatch_leaves writes each evaluator's dense batch (any pointer may be NULL) and the rows each holds."""
+    _fields_ = [("boards", C.c_void_p * 2), ("sides", C.c_void_p * 2), ("waiting", C.c_void_p * 2), ("lanes", C.c_void_p * 2), ("cap", C.c_uint32 * 2)]
+
+
+class TaflMatchStats(C.Structure):
+    """tafl_match_stats: games[a][r], the episodes closed or cut while evaluator a played the attackers; r = attacker win, defender win,
+    draw, cut."""
+    _fields_ = [("games", (C.c_uint64 * 4) * 2), ("_reserved", C.c_uint64 * 8)]
+
+
 class TaflExamplesStats(C.Structure):
     _fields_ = [("dropped", C.c_uint64), ("overflowed", C.c_uint64), ("bad_index", C.c_uint64), ("device_bytes", C.c_uint64)]
 
@@ -182,14 +198,16 @@ class TaflExamplesStats(C.Structure):
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
                   "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
-                  "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64}
+                  "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64, "tafl_match_opts": 32, "tafl_match_io": 72,
+                  "tafl_match_stats": 128}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
                     ("tafl_mcts_stats", TaflMctsStats), ("tafl_gmcts_stats", TaflGmctsStats),
                     ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats),
                     ("tafl_root_noise", TaflRootNoise), ("tafl_episode_opts", TaflEpisodeOpts),
-                    ("tafl_episode_stats", TaflEpisodeStats)]:
+                    ("tafl_episode_stats", TaflEpisodeStats), ("tafl_match_opts", TaflMatchOpts), ("tafl_match_io", TaflMatchIo),
+                    ("tafl_match_stats", TaflMatchStats)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

@@ -207,6 +207,112 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_reopen(GuidedMem M, Qu
     if (Guided<NL, W>::selfplay_reopen(M, g, soa, sp, ep, rec)) atomicAdd(&stats[GS_WAITING], 1ull);
 }
 
+// ---- match play: two evaluators in an episodes run (tafl_gmatch_*) -----------------------------------------------
+// The evaluators' dense batches are a stable two-way partition of the waiting lanes by owner (Guided::match_owner), in two launches of
+// 256-lane workgroups.  k_gmatch_rank: the rank of a lane among the lanes of its workgroup with the same owner - a wave ballot and mbcnt
+// inside the wave, the four wave counts through LDS - goes to row_of, the workgroup's two counts to block_counts.  k_gmatch_place: every
+// workgroup sums the counts of the workgroups before it (and all of them: the totals), adds its offset to the ranks and writes
+// lanes[e][row].  No atomic decides a row, so the rows are in ascending lane order.
+#define TAFL_MATCH_BLOCK 256
+#define TAFL_MATCH_WAVES (TAFL_MATCH_BLOCK / 64)
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_MATCH_BLOCK) void k_gmatch_rank(GuidedMem M, const Quad* soa, const uint32_t* episode, uint64_t game_id_base, uint32_t swap, uint32_t* row_of,
+                                                                  uint32_t* block_counts) {
+    __shared__ uint32_t wave_cnt[2][TAFL_MATCH_WAVES];
+    const uint32_t g = blockIdx.x * TAFL_MATCH_BLOCK + threadIdx.x, wave = threadIdx.x >> 6;
+    uint32_t e = 2u;                                               // 2: the lane does not wait
+    if (g < M.G && M.kind[g] == 1) e = Guided<NL, W>::match_owner(game_id_base, g, episode[g], swap, Guided<NL, W>::batch_flags(soa, M.G, g));
+    const unsigned long long b0 = __ballot(e == 0u), b1 = __ballot(e == 1u), mine = e == 0u ? b0 : b1;
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(mine >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mine, 0u));
+    if ((threadIdx.x & 63u) == 0u) { wave_cnt[0][wave] = (uint32_t)__popcll(b0); wave_cnt[1][wave] = (uint32_t)__popcll(b1); }
+    __syncthreads();
+    if (e < 2u) {
+        uint32_t before = 0;
+        for (uint32_t w = 0; w < wave; ++w) before += wave_cnt[e][w];
+        row_of[g] = (e << 31) | (before + rank);
+    } else if (g < M.G) row_of[g] = kMatchNoRow;
+    if (threadIdx.x < 2u) {
+        uint32_t sum = 0;
+        for (uint32_t w = 0; w < TAFL_MATCH_WAVES; ++w) sum += wave_cnt[threadIdx.x][w];
+        block_counts[2u * blockIdx.x + threadIdx.x] = sum;
+    }
+}
+__global__ __launch_bounds__(TAFL_MATCH_BLOCK) void k_gmatch_place(uint32_t G, uint32_t n_blocks, const uint32_t* block_counts, uint32_t* row_of, uint32_t* lanes, uint32_t* counts) {
+    __shared__ uint32_t part[4][TAFL_MATCH_WAVES];                 // per wave: evaluator 0 / 1 before this workgroup, evaluator 0 / 1 in all
+    uint32_t s[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t t = threadIdx.x; t < n_blocks; t += TAFL_MATCH_BLOCK) {
+        const uint32_t c0 = block_counts[2u * t], c1 = block_counts[2u * t + 1u];
+        if (t < blockIdx.x) { s[0] += c0; s[1] += c1; }
+        s[2] += c0; s[3] += c1;
+    }
+    TAFL_UNROLL for (int k = 0; k < 4; ++k) {
+        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off);
+        if ((threadIdx.x & 63u) == 0u) part[k][threadIdx.x >> 6] = s[k];
+    }
+    __syncthreads();
+    uint32_t tot[4];
+    TAFL_UNROLL for (int k = 0; k < 4; ++k) { tot[k] = 0; for (uint32_t w = 0; w < TAFL_MATCH_WAVES; ++w) tot[k] += part[k][w]; }
+    const uint32_t g = blockIdx.x * TAFL_MATCH_BLOCK + threadIdx.x;
+    if (g < G) {
+        const uint32_t r = row_of[g];
+        if (r != kMatchNoRow) {
+            const uint32_t e = r >> 31, row = (r & kMatchRowMask) + tot[e];
+            if (row < G) { row_of[g] = (e << 31) | row; lanes[(size_t)e * G + row] = g; }      // (row < count_e <= G by construction)
+        }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) { counts[0] = tot[2]; counts[1] = tot[3]; }
+}
+// the evaluators' network input: k_gmcts_leaves with one thread per (row, tile) of the two compact batches, evaluator 0's rows first.  Rows
+// beyond the counts exit; the waiting flags are written up to each capacity.  The host has checked counts[e] <= cap[e].
+struct MatchOut { uint8_t* boards[2]; uint8_t* sides[2]; uint8_t* waiting[2]; uint32_t* lanes[2]; uint32_t cap[2]; };
+template <int NL, int W>
+__global__ __launch_bounds__(256) void k_gmatch_leaves(Consts<NL> C, GuidedMem M, const uint32_t* lanes, const uint32_t* counts, MatchOut o) {
+    const uint32_t nn = C.n * C.n;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, threads = (size_t)gridDim.x * 256;
+    const uint32_t cnt[2] = {counts[0], counts[1]};
+    TAFL_UNROLL for (int e = 0; e < 2; ++e)
+        if (o.waiting[e]) for (size_t r = i; r < o.cap[e]; r += threads) o.waiting[e][r] = r < cnt[e] ? 1 : 0;
+    if (i >= (size_t)M.G * nn) return;
+    const uint32_t R = (uint32_t)(i / nn), t = (uint32_t)(i % nn), r = t / C.n, c = t % C.n, bit = r * (uint32_t)W + c;
+    if (R >= cnt[0] + cnt[1] || cnt[0] > M.G || cnt[1] > M.G) return;
+    const uint32_t e = R >= cnt[0] ? 1u : 0u, row = e ? R - cnt[0] : R;
+    if (row >= o.cap[e]) return;
+    const uint32_t g = lanes[(size_t)e * M.G + row];
+    if (g >= M.G) return;
+    const uint32_t L = M.leaf[g];
+    const uint32_t* rec = (const uint32_t*)(M.node_state + ((size_t)L * M.G + g) * StateIO<NL>::QUADS);   // att[NL], def[NL], rep[4], meta[4]
+    const uint32_t aw = rec[bit >> 5], dw = rec[NL + (bit >> 5)], flags = rec[2 * NL + 7];
+    if (o.boards[e]) o.boards[e][(size_t)row * nn + t] = (uint8_t)board_value((aw >> (bit & 31)) & 1u, (dw >> (bit & 31)) & 1u, r, c, C.n, flags);
+    if (t == 0) {
+        if (o.sides[e]) o.sides[e][row] = (uint8_t)((flags & TAFL_F_SIDE) ? TAFL_DEFENDER : TAFL_ATTACKER);
+        if (o.lanes[e]) o.lanes[e][row] = g;
+    }
+}
+// the round of a match run: k_gselfplay_episodes with the lane's evaluation read from its row of its owner's compact batch
+struct MatchIn { const float* priors[2]; const float* values[2]; };
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmatch_round(Consts<NL> C, GuidedMem M, Quad* soa, MatchIn in, const uint32_t* row_of, uint32_t A, double c_puct,
+                                                             uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    const uint32_t r = row_of[g];
+    const float* pr = nullptr; float v = 0.f;
+    if (r != kMatchNoRow) {
+        const float* p = in.priors[r >> 31]; const float* vs = in.values[r >> 31];
+        if (p && vs) { pr = p + (size_t)(r & kMatchRowMask) * A; v = vs[r & kMatchRowMask]; }
+    }
+    Guided<NL, W>::selfplay_step_episodes(M, g, soa, pr, v, A, c_puct, n_sims, sp, ep, rec, C, gs);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
+// the tally, between the round and k_gselfplay_reopen on the same stream (Guided::match_tally)
+template <int NL, int W>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmatch_tally(GuidedMem M, const Quad* soa, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, GMatch mt) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    Guided<NL, W>::match_tally(M, g, soa, sp, ep, rec, mt);
+}
+
 // the arena of a search from fresh roots: max_sims + 1 nodes and (max_sims + 1) x edges_per_node edges per game; the guided stats are zeroed
 static int gmcts_arena(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_node, const char* name) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n; const size_t q = (size_t)quads_of(c);
@@ -492,6 +598,7 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
             return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin_episodes: the openings batch has another size, board or device");
     }
     b->gsp_active = false; b->gsp_has = false;                 // (a begin that fails from here on leaves no run to step, end or ask for stats)
+    b->gm_on = false; b->gm_leaves = false;                    // (tafl_gmatch_begin marks its run after this function)
     if (const int rc = join_search(b)) return rc;
     if (eo && openings != b) {
         if (const int rc = join_search(openings)) return rc;
@@ -558,6 +665,7 @@ int tafl_gselfplay_episode_stats(tafl_batch* b, uint32_t* out_episodes, tafl_epi
 
 int tafl_gselfplay_step(tafl_batch* b, const float* priors, const float* values, int in_is_device, uint32_t* out_waiting) {
     if (!b || !b->gsp_active) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: no run is open on this batch (tafl_gselfplay_begin first; a write to the batch states closes a run)");
+    if (b->gm_on) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: the open run is a match (tafl_gmatch_leaves / tafl_gmatch_step)");
     if ((priors == nullptr) != (values == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: priors and values go together");
     if (b->gsp_first != (priors == nullptr)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_step: the first step after tafl_gselfplay_begin, and only that one, takes priors = values = NULL");
     HIPCHK(hipSetDevice(b->ctx->device));
@@ -576,6 +684,126 @@ int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves)
     COPY_OUT(out_moves, b->gsp_moves_done.p, n, c->stream);
     HIPCHK(hipStreamSynchronize(c->stream));
     if (out_moves) for (uint32_t g = 0; g < n; ++g) out_moves[g] &= ~(kGspStopped | kGspEpisodeEnded);
+    return TAFL_OK;
+}
+
+// ---- match play: two evaluators in an episodes run ---------------------------------------------------------------
+int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* o, uint32_t n_moves, uint64_t game_id_base,
+                      tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings, const tafl_match_opts* mo) {
+    if (!b || !eo || !mo) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_begin: bad argument");
+    if (mo->swap > 1u) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_begin: swap must be 0 or 1");
+    if (mo->flags != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
+    for (uint32_t r : mo->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
+    if (b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: root noise is set on the batch (tafl_gmcts_set_root_noise(NULL) first)");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    if (const int rc = gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b)) return rc;
+    b->gsp_active = false; b->gsp_has = false;                 // (the run counts as open once its match buffers exist)
+    const uint32_t n_blocks = (n + TAFL_MATCH_BLOCK - 1) / TAFL_MATCH_BLOCK;
+    NEED(b->gm_row_of, sizeof(uint32_t) * (size_t)n); NEED(b->gm_lanes, sizeof(uint32_t) * 2 * (size_t)n); NEED(b->gm_blocks, sizeof(uint32_t) * 2 * (size_t)n_blocks);
+    NEED(b->gm_counts, sizeof(uint32_t) * 2); NEED(b->gm_games, sizeof(unsigned long long) * 2 * EP_COUNT);
+    b->gm.swap = mo->swap; b->gm_row_of.bind(b->gm.row_of); b->gm_games.bind(b->gm.games);
+    HIPCHK(hipMemsetAsync(b->gm_games.p, 0, sizeof(unsigned long long) * 2 * EP_COUNT, c->stream));
+    b->gsp_has = true; b->gsp_active = true; b->gsp_first = false; b->gm_on = true; b->gm_leaves = false;
+    return TAFL_OK;
+}
+
+int tafl_gmatch_leaves(tafl_batch* b, const tafl_match_io* io, int out_is_device, uint32_t out_count[2]) {
+    if (!b || !b->gsp_active || !b->gm_on) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_leaves: no match run is open on this batch (tafl_gmatch_begin first; a write to the batch states closes a run)");
+    if (!io || !out_count) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_leaves: null argument");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, nn = (uint32_t)c->n * c->n;
+    const uint32_t n_blocks = (n + TAFL_MATCH_BLOCK - 1) / TAFL_MATCH_BLOCK;
+    HIPCHK(hipSetDevice(c->device));
+    b->gm_leaves = false;
+    uint32_t* row_of = b->gm_row_of.as<uint32_t>(); uint32_t* lanes = b->gm_lanes.as<uint32_t>(); uint32_t* blocks = b->gm_blocks.as<uint32_t>(); uint32_t* counts = b->gm_counts.as<uint32_t>();
+    dispatch<BATCH, false>(c, [&](auto t) {
+        hipLaunchKernelGGL((k_gmatch_rank<t.NL, t.W>), dim3(n_blocks), dim3(TAFL_MATCH_BLOCK), 0, c->stream, b->gmem, (const Quad*)b->soa, (const uint32_t*)b->gsp_ep.episode,
+                           b->gsp_rec.game_id_base, b->gm.swap, row_of, blocks); });
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_gmatch_place, dim3(n_blocks), dim3(TAFL_MATCH_BLOCK), 0, c->stream, n, n_blocks, (const uint32_t*)blocks, row_of, lanes, counts);
+    HIPCHK(hipGetLastError());
+    uint32_t cnt[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(cnt, counts, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out_count[0] = cnt[0]; out_count[1] = cnt[1];
+    if (cnt[0] > io->cap[0] || cnt[1] > io->cap[1]) return fail(TAFL_ERR_CAPACITY, "tafl_gmatch_leaves: an evaluator has more waiting leaves than its cap (cap = batch size is always enough)");
+    // host pointers: the rows are staged behind one another in the buffers of tafl_gmcts_leaves (count_0 + count_1 <= n) and the waiting
+    // flags are written on the host
+    MatchOut mo;
+    for (int e = 0; e < 2; ++e) {
+        mo.boards[e] = io->boards[e]; mo.sides[e] = io->sides[e]; mo.waiting[e] = out_is_device ? io->waiting[e] : nullptr; mo.lanes[e] = out_is_device ? io->lanes[e] : nullptr;
+        mo.cap[e] = io->cap[e];
+    }
+    if (!out_is_device) {
+        NEED(b->g_boards, (size_t)n * nn); NEED(b->g_sides, n);
+        for (int e = 0; e < 2; ++e) {
+            const uint32_t first = e ? cnt[0] : 0u;
+            if (io->boards[e]) mo.boards[e] = b->g_boards.as<uint8_t>() + (size_t)first * nn;
+            if (io->sides[e]) mo.sides[e] = b->g_sides.as<uint8_t>() + first;
+        }
+    }
+    const size_t total = (size_t)n * nn;
+    dispatch<BATCH, false>(c, [&](auto t) {
+        hipLaunchKernelGGL((k_gmatch_leaves<t.NL, t.W>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, t.CC, b->gmem, (const uint32_t*)lanes, (const uint32_t*)counts, mo); });
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) {
+        for (int e = 0; e < 2; ++e) {
+            if (cnt[e]) {
+                COPY_OUT(io->boards[e], mo.boards[e], (size_t)cnt[e] * nn, c->stream);
+                COPY_OUT(io->sides[e], mo.sides[e], cnt[e], c->stream);
+                COPY_OUT(io->lanes[e], lanes + (size_t)e * n, cnt[e], c->stream);
+            }
+            if (io->waiting[e]) for (uint32_t r = 0; r < io->cap[e]; ++r) io->waiting[e][r] = r < cnt[e] ? 1 : 0;
+        }
+    }
+    if (const int rc = sync_ok(c)) return rc;
+    b->gm_count[0] = cnt[0]; b->gm_count[1] = cnt[1]; b->gm_leaves = true;
+    return TAFL_OK;
+}
+
+int tafl_gmatch_step(tafl_batch* b, const float* const priors[2], const float* const values[2], int in_is_device) {
+    if (!b || !b->gsp_active || !b->gm_on) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_step: no match run is open on this batch (tafl_gmatch_begin first; a write to the batch states closes a run)");
+    if (!b->gm_leaves) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_step: tafl_gmatch_leaves first (once per step)");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
+    MatchIn in;
+    for (int e = 0; e < 2; ++e) {
+        in.priors[e] = priors ? priors[e] : nullptr; in.values[e] = values ? values[e] : nullptr;
+        if (b->gm_count[e] && (!in.priors[e] || !in.values[e])) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_step: priors and values of an evaluator with waiting leaves are missing");
+        if (!b->gm_count[e]) in.priors[e] = in.values[e] = nullptr;
+    }
+    HIPCHK(hipSetDevice(c->device));
+    if (!in_is_device) {                                        // exactly count_e rows of each evaluator, behind one another in g_priors / g_values
+        const size_t rows = (size_t)b->gm_count[0] + b->gm_count[1];
+        NEED(b->g_priors, sizeof(float) * std::max<size_t>(rows, 1) * A); NEED(b->g_values, sizeof(float) * std::max<size_t>(rows, 1));
+        for (int e = 0; e < 2; ++e) {
+            if (!b->gm_count[e]) continue;
+            const size_t first = e ? b->gm_count[0] : 0u, cnt = b->gm_count[e];
+            float* dp = b->g_priors.as<float>() + first * A; float* dv = b->g_values.as<float>() + first;
+            HIPCHK(hipMemcpyAsync(dp, in.priors[e], sizeof(float) * cnt * A, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipMemcpyAsync(dv, in.values[e], sizeof(float) * cnt, hipMemcpyHostToDevice, c->stream));
+            in.priors[e] = dp; in.values[e] = dv;
+        }
+    }
+    b->gm_leaves = false;
+    unsigned long long* st = b->g_stats.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmatch_round<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, in, (const uint32_t*)b->gm.row_of, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+    HIPCHK(hipGetLastError());
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmatch_tally<t.NL, t.W>), c, n, b->gmem, (const Quad*)b->soa, b->gsp, b->gsp_ep, b->gsp_rec, b->gm); });
+    HIPCHK(hipGetLastError());
+    dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+    HIPCHK(hipGetLastError());
+    return in_is_device ? TAFL_OK : sync_ok(c);                // (host arrays may be reused once the call returns)
+}
+
+int tafl_gmatch_get_stats(tafl_batch* b, tafl_match_stats* out) {
+    if (!b || !b->gsp_has || !b->gm_on || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmatch_get_stats: tafl_gmatch_begin first");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[2 * EP_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->gm_games.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memset(out, 0, sizeof *out);
+    for (int a = 0; a < 2; ++a) for (int r = 0; r < EP_COUNT; ++r) out->games[a][r] = h[a * EP_COUNT + r];
     return TAFL_OK;
 }
 

@@ -73,6 +73,14 @@ struct GEpisodes {
     uint64_t id_stride;          // game id of episode k of lane g = game_id_base + k * id_stride + g
     uint32_t* open_from;         // [G] of the examples object (null: nothing is recorded): first example of the lane's open episode
 };
+// what a match run (tafl_gmatch_begin) adds to an episodes run: an argument of the match kernels alone
+constexpr uint32_t kMatchNoRow = 0xFFFFFFFFu;    // GMatch::row_of: the lane has no row in either evaluator's batch
+constexpr uint32_t kMatchRowMask = 0x7FFFFFFFu;  // otherwise evaluator << 31 | row
+struct GMatch {
+    uint32_t swap;               // 0 or 1: which evaluator takes the attackers in episode 0 of the lane with the even global number
+    uint32_t* row_of;            // [G] where the evaluation of the lane's waiting leaf stands (tafl_gmatch_leaves writes it)
+    unsigned long long* games;   // [2 * EP_COUNT]: games[a * EP_COUNT + r], episodes closed or cut with evaluator a as the attackers
+};
 // Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
 struct RootNoise {
     double alpha, epsilon;
@@ -505,6 +513,26 @@ struct Guided {
         root_waits(M, g, st);
         ep.ep_start[g] = moves; sp.moves_done[g] = moves;
         return true;
+    }
+
+    // ---- match play: two evaluators in an episodes run (tafl_gmatch_*) ---------------------------------------
+    // the flags word of lane g's batch state alone (the last word of the last quad plane)
+    static TAFL_HD uint32_t batch_flags(const Quad* soa, uint32_t G, uint32_t g) { return soa[(size_t)(IO::QUADS - 1) * G + g].w; }
+    // the evaluator that plays the attackers in episode k of the lane with the global number game_id_base + g
+    static TAFL_HD uint32_t match_seat(uint64_t game_id_base, uint32_t g, uint32_t k, uint32_t swap) { return (uint32_t)((game_id_base + g + k + swap) & 1u); }
+    // the evaluator of every leaf of the lane's current search: the one that owns the side to move at the search's root, which is the
+    // lane's batch state (`flags` is its flags word)
+    static TAFL_HD uint32_t match_owner(uint64_t game_id_base, uint32_t g, uint32_t k, uint32_t swap, uint32_t flags) {
+        return (match_seat(game_id_base, g, k, swap) + ((flags & TAFL_F_SIDE) ? 1u : 0u)) & 1u;
+    }
+    // between the round and selfplay_reopen: a lane whose episode the round closed or cut counts it for the evaluator that played the
+    // attackers, the result read from the batch state as selfplay_reopen reads it (ep.episode[g] is still the number of that episode)
+    static TAFL_HD void match_tally(const GuidedMem& M, uint32_t g, const Quad* soa, const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const GMatch& mt) {
+        const uint32_t md = sp.moves_done[g];
+        if (!(md & kGspEpisodeEnded) || (md & kGspStopped)) return;
+        const uint32_t flags = batch_flags(soa, M.G, g), status = TAFL_F_STATUS(flags);
+        const uint32_t what = status == TAFL_STATUS_ONGOING ? (uint32_t)EP_CUT : status == TAFL_STATUS_DRAW ? (uint32_t)EP_DRAW : TAFL_F_WINNER(flags) != 0u ? (uint32_t)EP_DEFENDER : (uint32_t)EP_ATTACKER;
+        TAFL_COUNT_ADD(&mt.games[match_seat(rec.game_id_base, g, ep.episode[g], mt.swap) * EP_COUNT + what], 1);
     }
 };
 

@@ -230,6 +230,11 @@ struct tafl_batch {
     // (quad-plane SoA like the batch states) and the four result counters; gsp_episodes: the run that is open, or was last, is one
     bool gsp_episodes = false; GEpisodes gsp_ep = {};
     DevBuf gsp_episode, gsp_ep_start, gsp_openings, gsp_ep_counters;
+    // a match run (tafl_gmatch_begin): gm_on: the run that is open, or was last, is one; gm_leaves: tafl_gmatch_leaves has run since the
+    // last step, gm_count holds its counts and gm_row_of every lane's row; the lanes of the two compact batches [2][n], the partition's
+    // workgroup counts, its two totals, the tally [2][4]
+    bool gm_on = false, gm_leaves = false; GMatch gm = {}; uint32_t gm_count[2] = {0, 0};
+    DevBuf gm_row_of, gm_lanes, gm_blocks, gm_counts, gm_games;
     // Dirichlet noise at the root (tafl_gmcts_set_root_noise): the setting, and what the open search or run latched at its begin
     bool noise_set = false, g_noise_on = false;
     tafl_root_noise noise_cfg = {}; RootNoise g_noise = {};

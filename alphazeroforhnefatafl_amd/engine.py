@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
 
 KC_MOVEGEN, KC_STEP, KC_ROLLOUT, KC_MCTS_TREE, KC_MCTS_ROLLOUT = range(5)
@@ -374,6 +374,66 @@ class GameBatch:
         moves = (C.c_uint32 * self.n)()
         check(lib().tafl_gselfplay_end(self._h, plays, moves))
         return plays, moves
+
+    # -- match play: two evaluators in an episodes run (include/taflhip.h tafl_gmatch_*) ----------------------------------------
+    def gmatch_begin(self, examples: "Examples | None", lane_moves: int, n_sims: int, c_puct: float = 1.0, edges_per_node: int = 256,
+                     game_id_base: int = 0, sample_seed: int = 0, temp_moves: int = 0, episode_moves: int = 0, id_stride: int = 0,
+                     openings: "GameBatch | None" = None, swap: int = 0):
+        """Opens a match run (tafl_gmatch_begin): gselfplay_begin_episodes with two evaluators.  In episode k of lane g evaluator
+        (game_id_base + g + k + swap) & 1 plays the attackers, and every search is evaluated by the evaluator that owns the side to move
+        at its root.  The loop is gmatch_leaves -> the evaluators -> gmatch_step until both counts are 0; gselfplay_end,
+        gselfplay_episode_stats, gmcts_leaves and gmcts_stats serve the run as they serve an episodes run.  Refused while root noise is set."""
+        o = TaflSelfplayOpts(sample_seed, temp_moves, 0, 0)
+        eo = TaflEpisodeOpts(id_stride, episode_moves, 0)
+        mo = TaflMatchOpts(swap, 0)
+        check(lib().tafl_gmatch_begin(self._h, n_sims, edges_per_node, c_puct, C.byref(o), lane_moves, game_id_base,
+                                      examples._h if examples is not None else None, C.byref(eo), openings._h if openings is not None else None, C.byref(mo)))
+        self._gsp_moves = lane_moves
+
+    def gmatch_leaves(self, buffers=None, cap: int | None = None):
+        """Each evaluator's dense batch of its waiting leaves, rows in ascending lane order (tafl_gmatch_leaves).  Host route
+        (buffers None): returns (counts, boards, sides, waiting, lanes), the last four pairs of numpy arrays with `cap` rows (default:
+        the batch size), of which the first counts[e] of evaluator e are written (waiting: all `cap`); the arrays are reused by the next
+        call.  Device route: `buffers` = one (boards_ptr, sides_ptr, waiting_ptr, lanes_ptr, cap) per evaluator (any pointer None) and
+        only (count_0, count_1) comes back.  A count above its cap raises TaflError (TAFL_ERR_CAPACITY) and writes nothing."""
+        io, cnt = TaflMatchIo(), (C.c_uint32 * 2)()
+        if buffers is not None:
+            for e in range(2):
+                io.boards[e], io.sides[e], io.waiting[e], io.lanes[e], io.cap[e] = buffers[e]
+            check(lib().tafl_gmatch_leaves(self._h, C.byref(io), 1, cnt))
+            return cnt[0], cnt[1]
+        import numpy as np
+        cap = self.n if cap is None else cap
+        s = self.logic.side_len
+        held = getattr(self, "_gm_host", None)
+        if held is None or held[0] != cap:
+            held = self._gm_host = (cap, [np.zeros((cap, s, s), np.uint8) for _ in range(2)], [np.zeros(cap, np.uint8) for _ in range(2)],
+                                    [np.zeros(cap, np.uint8) for _ in range(2)], [np.zeros(cap, np.uint32) for _ in range(2)])
+        _cap, boards, sides, waiting, lanes = held
+        for e in range(2):
+            io.boards[e], io.sides[e], io.waiting[e], io.lanes[e] = (a[e].ctypes.data for a in (boards, sides, waiting, lanes))
+            io.cap[e] = cap
+        check(lib().tafl_gmatch_leaves(self._h, C.byref(io), 0, cnt))
+        return (cnt[0], cnt[1]), boards, sides, waiting, lanes
+
+    def gmatch_step(self, priors, values, device: bool = False):
+        """One round of the match: priors[e] (float32 [count_e, action_size]) and values[e] (float32 [count_e]) in the row order of the
+        preceding gmatch_leaves, as ctypes float pointers or arrays (host) or integer device pointers (device=True); None for an
+        evaluator without waiting leaves.  Runs the round, the tally and the close-and-reopen."""
+        def ptrs(pair):
+            out = (C.c_void_p * 2)()
+            for e in range(2):
+                x = pair[e]
+                out[e] = None if x is None else x if isinstance(x, int) else C.cast(x, C.c_void_p)
+            return out
+        check(lib().tafl_gmatch_step(self._h, ptrs(priors), ptrs(values), int(device)))
+
+    def gmatch_stats(self) -> TaflMatchStats:
+        """games[a][r]: the episodes the match closed or cut while evaluator a played the attackers; r = attacker win, defender win,
+        draw, cut (a game that ends on the lane's last budgeted move stays open and is not counted)."""
+        st = TaflMatchStats()
+        check(lib().tafl_gmatch_get_stats(self._h, C.byref(st)))
+        return st
 
     # -- Dirichlet noise at the root of a guided search (include/taflhip.h tafl_root_noise) ----------------------------------
     def set_root_noise(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0):

@@ -12,6 +12,72 @@ from .engine import Examples, GameBatch
 from .mcts import MCTSArgs, apply_root_noise
 
 
+class MatchResult:
+    """What play_match returns.  games[a][r]: the episodes closed or cut while evaluator a played the attackers, r = attacker win, defender
+    win, draw, cut.  wins_as_attacker[e] / wins_as_defender[e]: evaluator e's wins by colour; draws, cut, games: over both seats (games
+    counts the cut ones too); score: evaluator 0's (wins + draws / 2) / (games - cut), None when no game was played to its end."""
+
+    def __init__(self, games):
+        self.games = [[int(x) for x in row] for row in games]
+        g = self.games
+        self.wins_as_attacker = (g[0][0], g[1][0])
+        self.wins_as_defender = (g[1][1], g[0][1])          # evaluator e defends in the games whose attacker is 1 - e
+        self.draws, self.cut = g[0][2] + g[1][2], g[0][3] + g[1][3]
+        self.games_played = sum(g[0]) + sum(g[1])
+        decided = self.games_played - self.cut
+        self.score = (self.wins_as_attacker[0] + self.wins_as_defender[0] + 0.5 * self.draws) / decided if decided else None
+
+    def __repr__(self):
+        return (f"MatchResult(wins_as_attacker={self.wins_as_attacker}, wins_as_defender={self.wins_as_defender}, draws={self.draws}, cut={self.cut}, "
+                f"games={self.games_played}, score={self.score})")
+
+
+def play_match(batch: GameBatch, nets, args: MCTSArgs, lane_moves: int, *, examples: Examples | None = None, openings: GameBatch | None = None,
+               episode_moves: int = 0, swap: int = 0, temp_moves: int = 0, sample_seed: int = 1, game_id_base: int = 0, id_stride: int = 0,
+               edges_per_node: int = 256, device: bool = False, buffers=None, row_multiple: int = 1) -> MatchResult:
+    """A match between the evaluators nets[0] and nets[1] (include/taflhip.h tafl_gmatch_*): the episodes run of
+    play_guided_selfplay in which, in episode k of lane g, evaluator (game_id_base + g + k + swap) & 1 plays the attackers, and every
+    search is evaluated by the network that owns the side to move at its root.  Both speak predict_batch(boards, sides, waiting) ->
+    (priors, values).  Net e is called with the first m_e rows of its buffers - its waiting leaves in ascending lane order, m_e = their
+    number rounded up to `row_multiple` and capped at the batch size, so that a compiled network sees few distinct shapes - and a net
+    without waiting leaves is not called.  Host route: numpy arrays go in; (priors, values) are numpy float32 arrays, ctypes float
+    arrays or pointers.  device=True: `buffers` = one (boards, sides, waiting, lanes) of torch tensors on the batch's device per
+    evaluator (uint8 [n, side, side], uint8 [n], uint8 [n], int32 [n]); the net gets row views of the first three and returns integer
+    device pointers.  The loop is leaves -> up to two networks -> step until nothing waits, then gselfplay_end.  args.dirichletEpsilon
+    must be 0: a match takes no root noise."""
+    if args.dirichletEpsilon:
+        raise ValueError("play_match: a match takes no root noise (args.dirichletEpsilon must be 0)")
+    n = batch.n
+    batch.clear_root_noise()
+    batch.gmatch_begin(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
+                       temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings, swap=swap)
+    ptrs = None
+    if device:
+        ptrs = [tuple(t.data_ptr() for t in buffers[e]) + (n,) for e in range(2)]
+    while True:
+        if device:
+            counts = batch.gmatch_leaves(ptrs)
+            rows = [buffers[e][:3] for e in range(2)]
+        else:
+            counts, boards, sides, waiting, _lanes = batch.gmatch_leaves()
+            rows = [(boards[e], sides[e], waiting[e]) for e in range(2)]
+        if not (counts[0] or counts[1]):
+            break
+        priors, values = [None, None], [None, None]
+        for e in range(2):
+            if counts[e]:
+                m = min(n, -(-counts[e] // row_multiple) * row_multiple)
+                priors[e], values[e] = nets[e].predict_batch(*(a[:m] for a in rows[e]))
+        batch.gmatch_step([_fptr(p) for p in priors], [_fptr(v) for v in values], device=device)
+    batch.gselfplay_end(want_plays=False)
+    return MatchResult(batch.gmatch_stats().games)
+
+
+def _fptr(a):
+    """A float32 numpy array as its data pointer; anything else (None, a ctypes array or pointer, an integer device pointer) as it is."""
+    return a.ctypes.data_as(C.POINTER(C.c_float)) if isinstance(a, np.ndarray) else a
+
+
 def _games_over(batch: GameBatch) -> int:
     """Games of the batch that are over (one download, the status bytes counted as an array)."""
     st = np.frombuffer(batch.download(), dtype=np.uint8).reshape(batch.n, C.sizeof(TaflState))

@@ -613,6 +613,72 @@ int tafl_gselfplay_begin_episodes(tafl_batch* b, uint32_t n_sims, uint32_t edges
                                   uint32_t n_moves, uint64_t game_id_base, tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings);
 int tafl_gselfplay_episode_stats(tafl_batch* b, uint32_t* out_episodes, tafl_episode_stats* out);
 
+/* ---- match play: two evaluators play each other in an episodes run -----------------------------------------------
+ * The step that decides whether a newly trained network replaces the old one: games between two evaluators, 0 and 1, colours alternating,
+ * results tallied by seat.  A match run IS an episodes run - budget, openings, id_stride, episode_moves, temp_moves, sample_seed, examples,
+ * closing and reopening all as tafl_gselfplay_begin_episodes defines them - in which every search is run with the evaluator that owns the
+ * side to move at its root.  A guided search starts from a fresh root at every move, so there is no second tree: the device routes each
+ * waiting leaf to its evaluator, hands each evaluator a dense batch of only its own leaves, reads the answers back by row and tallies.
+ * Build-defined (the reference has no arena); alpha-zero-general's Arena is the model: each player searches with its own network, also at
+ * the opponent's nodes inside its own search.
+ *
+ *   seat          in episode k of lane g, evaluator seat(g, k) = (game_id_base + g + k + swap) & 1 plays the attackers and the other one
+ *                 the defenders; swap is 0 or 1.  Neighbouring lanes start with opposite colours, a lane alternates colours from episode to
+ *                 episode, and the rule does not depend on the sharding (game_id_base + g is the lane's global number).
+ *   owner         every leaf of a lane's current search is evaluated by owner(g) = (seat(g, k) + s) & 1, s = 0 if the attackers are to
+ *                 move at the search's root and 1 if the defenders are.  The root is the lane's batch state.
+ *   equivalence   a match run with the evaluators (f0, f1) leaves exactly what the tafl_gselfplay_begin_episodes run with the same
+ *                 arguments leaves when that run's evaluator answers lane g's waiting leaf with f_owner(g)(leaf): the plays, the moves per
+ *                 lane, the final batch states, every example field, z, final, open_from, tafl_episode_stats, the per-lane episode counts
+ *                 and tafl_gmcts_stats.sims / predicts / terminal_hits / faults.  The search arithmetic, the pick rule, the record and
+ *                 close / cut / reopen are untouched.
+ *   root noise    evaluation matches do not use it: tafl_gmatch_begin fails with TAFL_ERR_UNSUPPORTED while root noise is set on the batch.
+ *
+ * The host loop is  tafl_gmatch_begin; for (;;) { tafl_gmatch_leaves; if both counts are 0: break; evaluator e on its count_e rows (e = 0, 1);
+ * tafl_gmatch_step }; tafl_gselfplay_end; tafl_gmatch_get_stats.
+ *
+ * tafl_gmatch_begin does what tafl_gselfplay_begin_episodes does, first round included, and marks the run as a match.  Everything that call
+ *   rejects is rejected alike; mo->swap > 1: TAFL_ERR_INVALID_ARG; non-zero mo->flags or reserved words: TAFL_ERR_UNSUPPORTED.
+ * tafl_gmatch_leaves writes, for each evaluator e, a dense batch of its waiting leaves.  Row r of evaluator e is the r-th lane, in ascending
+ *   lane order, that waits and has owner == e:  lanes[e][r] is that lane, boards[e][r * side_len^2 ..] and sides[e][r] are exactly what
+ *   tafl_gmcts_leaves writes for that lane, and waiting[e][r] = (r < count_e) for every r < cap[e].  Rows at and beyond count_e of boards,
+ *   sides and lanes are not written.  Any pointer of `io` may be NULL; out_is_device as in tafl_gmcts_leaves.  out_count gets the two
+ *   counts: their sum is tafl_gmcts_stats.waiting, and both zero means the run is complete.  count_e > cap[e] (whichever pointers are
+ *   given): TAFL_ERR_CAPACITY, nothing is written but out_count, and the call may be repeated; cap = the batch size is always enough.  The
+ *   call also records each lane's row for the next step, in a buffer of the batch.
+ * tafl_gmatch_step: priors[e] holds count_e rows of tafl_action_size float32 and values[e] count_e floats, in the row order of the preceding
+ *   tafl_gmatch_leaves.  Host pointers: exactly count_e rows are staged; device pointers are used in place.  priors[e] and values[e] may be
+ *   NULL when count_e == 0 (and are not read then).  A step without a successful tafl_gmatch_leaves since the last step or the begin:
+ *   TAFL_ERR_INVALID_ARG.  It runs the round, the tally, and the close-and-reopen.
+ * tafl_gmatch_get_stats: games[a][r] counts the episodes the run closed or cut while evaluator a played the attackers; r is attacker win,
+ *   defender win, draw, cut - the four cases of tafl_episode_stats, and games[0][r] + games[1][r] equals that struct's field for every r.
+ *   A game that ends on the lane's last budgeted move stays open and is not counted, as in an episodes run.  Valid from the begin until the
+ *   next tafl_gselfplay_begin / _begin_episodes / tafl_gmatch_begin on the batch.
+ * tafl_gselfplay_step on a match run, and tafl_gmatch_leaves / _step / _get_stats without a match run, fail with TAFL_ERR_INVALID_ARG.
+ *   tafl_gmcts_leaves, tafl_gmcts_get_stats, tafl_gselfplay_episode_stats and tafl_gselfplay_end serve a match run as they serve an episodes
+ *   run, and what closes an episodes run closes a match run.  Not offered: more than two evaluators, root noise, subtree reuse. */
+typedef struct tafl_match_opts {
+    uint32_t swap;             /* 0 or 1 */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[6];     /* 0 */
+} tafl_match_opts;             /* 32 bytes */
+typedef struct tafl_match_io {
+    uint8_t*  boards[2];       /* [cap[e] * side_len^2] */
+    uint8_t*  sides[2];        /* [cap[e]] */
+    uint8_t*  waiting[2];      /* [cap[e]] */
+    uint32_t* lanes[2];        /* [cap[e]] */
+    uint32_t  cap[2];          /* rows each evaluator's buffers hold */
+} tafl_match_io;
+typedef struct tafl_match_stats {
+    uint64_t games[2][4];      /* [evaluator that played the attackers][attacker win, defender win, draw, cut] */
+    uint64_t _reserved[8];
+} tafl_match_stats;            /* 128 bytes */
+int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, double c_puct, const tafl_selfplay_opts* opts, uint32_t n_moves,
+                      uint64_t game_id_base, tafl_examples* ex, const tafl_episode_opts* eo, tafl_batch* openings, const tafl_match_opts* mo);
+int tafl_gmatch_leaves(tafl_batch* b, const tafl_match_io* io, int out_is_device, uint32_t out_count[2]);
+int tafl_gmatch_step(tafl_batch* b, const float* const priors[2], const float* const values[2], int in_is_device);
+int tafl_gmatch_get_stats(tafl_batch* b, tafl_match_stats* out);
+
 /* ---- Dirichlet noise at the root of a guided search --------------------------------------------------------------
  * AlphaZero's root exploration noise, P' = (1 - epsilon) P + epsilon eta with eta ~ Dir(alpha), for tafl_gmcts_* searches from fresh
  * roots and for tafl_gselfplay_* runs.  Build-defined (the reference has a TODO, src/mcts.rs:53).  Off by default; with it off nothing
