@@ -7,7 +7,7 @@ from . import abi
 from .abi import Ruleset, boards, rules
 
 __all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples",
-           "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult"]
+           "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult", "playout_cap_is_full"]
 
 
 def __getattr__(name):
@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("BatchedGameLogic", "GameBatch", "Examples"):
         from . import engine
         return getattr(engine, name)
-    if name in ("MCTS", "MCTSArgs", "GuidedMCTS"):
+    if name in ("MCTS", "MCTSArgs", "GuidedMCTS", "playout_cap_is_full"):
         from . import mcts
         return getattr(mcts, name)
     if name in ("play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult"):

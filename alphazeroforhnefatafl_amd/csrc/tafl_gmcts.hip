@@ -198,6 +198,18 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_episodes(Consts<NL> C,
     Guided<NL, W>::selfplay_step_episodes(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C, gs, nz);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+// the round of a capped run (tafl_gselfplay_set_playout_cap), plain or episodes, without or with root noise: kernels
+// of their own, so that the ones above stay as they are.  `ep` is read by the EPISODES instantiations alone, `nz` by the NOISE ones.
+template <int NL, int W, bool NOISE, bool EPISODES>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_capped(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                                 uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats, RootNoise nz, PlayoutCap pc) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::template selfplay_step_capped<NOISE, EPISODES>(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C,
+                                                                  gs, nz, pc);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
 // close and reopen, right after the round on the same stream: the lanes whose episode ended settle its examples, count it, take their
 // opening and wait with a fresh root (Guided::selfplay_reopen); every other lane leaves at its first load
 template <int NL, int W>
@@ -363,7 +375,36 @@ static RootNoise noise_arg(const tafl_root_noise& cfg) {
     return nz;
 }
 
+// a tafl_playout_cap the library accepts
+static int cap_check(const tafl_playout_cap* cfg) {
+    if (cfg->fast_sims < 2u || cfg->fast_sims > 0xFFFFu || cfg->full_per_65536 > 65536u)
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_playout_cap: fast_sims must be 2 .. 65535 and full_per_65536 at most 65536");
+    if (cfg->flags != 0 || cfg->_reserved[0] != 0 || cfg->_reserved[1] != 0 || cfg->_reserved[2] != 0)
+        return fail(TAFL_ERR_UNSUPPORTED, "tafl_playout_cap: flags and reserved words must be 0");
+    return TAFL_OK;
+}
+
 extern "C" {
+
+int tafl_gselfplay_set_playout_cap(tafl_batch* b, const tafl_playout_cap* cfg) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_playout_cap: null batch");
+    if (!cfg) { b->cap_set = false; return TAFL_OK; }
+    if (const int rc = cap_check(cfg)) return rc;
+    b->cap_set = true; b->cap_cfg = *cfg;
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_playout_cap_stats(tafl_batch* b, tafl_playout_cap_stats* out) {
+    if (!b || !b->gsp_has || !b->gsp_cap_on || !out) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_playout_cap_stats: no capped run on this batch (tafl_gselfplay_set_playout_cap, then a begin)");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[CAP_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->gsp_cap_counters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    memset(out, 0, sizeof *out);
+    out->full_moves = h[CAP_FULL]; out->fast_moves = h[CAP_FAST];
+    return TAFL_OK;
+}
 
 int tafl_gmcts_set_root_noise(tafl_batch* b, const tafl_root_noise* cfg) {
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_set_root_noise: null batch");
@@ -568,7 +609,18 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    if (b->gsp_episodes) {
+    if (b->gsp_cap_on) {                                        // a capped run: rounds of its own, then the reopen of an episodes run as below
+        const bool nz = b->g_noise_on, ep = b->gsp_episodes;
+#define TAFL_CAPPED(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_capped<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap); })
+        if (ep) { if (nz) TAFL_CAPPED(true, true); else TAFL_CAPPED(false, true); }
+        else { if (nz) TAFL_CAPPED(true, false); else TAFL_CAPPED(false, false); }
+#undef TAFL_CAPPED
+        if (ep) {
+            HIPCHK(hipGetLastError());
+            dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+        }
+    }
+    else if (b->gsp_episodes) {
         if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_episodes<t.NL, t.W, true>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise); });
         else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_episodes<t.NL, t.W>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st); });
         HIPCHK(hipGetLastError());
@@ -599,6 +651,7 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     }
     b->gsp_active = false; b->gsp_has = false;                 // (a begin that fails from here on leaves no run to step, end or ask for stats)
     b->gm_on = false; b->gm_leaves = false;                    // (tafl_gmatch_begin marks its run after this function)
+    if (b->cap_set && b->cap_cfg.fast_sims > n_sims) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_begin: the playout cap's fast_sims exceeds n_sims");
     if (const int rc = join_search(b)) return rc;
     if (eo && openings != b) {
         if (const int rc = join_search(openings)) return rc;
@@ -630,6 +683,13 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     b->gsp_sims = n_sims; b->gsp_cpuct = c_puct;
     b->g_noise_on = b->noise_set;                            // the run latches the noise setting; gid and M are the run's own
     if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
+    b->gsp_cap_on = b->cap_set; b->gsp_cap = PlayoutCap{};   // and the playout cap
+    if (b->cap_set) {
+        NEED(b->gsp_cap_counters, sizeof(unsigned long long) * CAP_COUNT);
+        HIPCHK(hipMemsetAsync(b->gsp_cap_counters.p, 0, sizeof(unsigned long long) * CAP_COUNT, c->stream));
+        b->gsp_cap.seed = b->cap_cfg.seed; b->gsp_cap.fast_sims = b->cap_cfg.fast_sims; b->gsp_cap.full_per_65536 = b->cap_cfg.full_per_65536;
+        b->gsp_cap_counters.bind(b->gsp_cap.counters);
+    }
     HIPCHK(hipMemsetAsync(b->gsp_plays.p, 0, sizeof(tafl_play) * (size_t)n * n_moves, c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_init<t.NL, t.W>), c, n, t.CC, b->soa, b->gmem, b->gsp); });
     HIPCHK(hipGetLastError());
@@ -695,6 +755,7 @@ int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, d
     if (mo->flags != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
     for (uint32_t r : mo->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
     if (b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: root noise is set on the batch (tafl_gmcts_set_root_noise(NULL) first)");
+    if (b->cap_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: a playout cap is set on the batch (tafl_gselfplay_set_playout_cap(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     if (const int rc = gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b)) return rc;
     b->gsp_active = false; b->gsp_has = false;                 // (the run counts as open once its match buffers exist)

@@ -81,6 +81,21 @@ struct GMatch {
     uint32_t* row_of;            // [G] where the evaluation of the lane's waiting leaf stands (tafl_gmatch_leaves writes it)
     unsigned long long* games;   // [2 * EP_COUNT]: games[a * EP_COUNT + r], episodes closed or cut with evaluator a as the attackers
 };
+// playout cap randomization (include/taflhip.h tafl_playout_cap): an argument of the capped rounds alone
+enum { CAP_FULL = 0, CAP_FAST, CAP_COUNT };
+struct PlayoutCap {
+    uint64_t seed;
+    uint32_t fast_sims;          // simulations of a fast move (a full one searches the run's n_sims)
+    uint32_t full_per_65536;     // a move is full iff the high 16 bits of its class word are below this
+    unsigned long long* counters;   // [CAP_COUNT] moves made per class
+};
+// the class of move M of game gid, a pure function of (seed, gid, M): the game key is that of selfplay_rand with kCapKey folded in, so for
+// equal seeds the class stream differs from the sample stream and from the noise stream
+constexpr uint64_t kCapKey = 0x504C41594F555443ull;
+static TAFL_HD bool cap_is_full(const PlayoutCap& pc, uint64_t gid, uint32_t move_no) {
+    using E = Engine<2, 7>;
+    return (E::ply_rand(E::sim_key(E::game_key(pc.seed, gid) ^ kCapKey, move_no), 0u) >> 16) < pc.full_per_65536;
+}
 // Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
 struct RootNoise {
     double alpha, epsilon;
@@ -208,9 +223,9 @@ struct Guided {
     // mcts.py:83-102 for the pending leaf, with the network's answer
     static TAFL_HD bool expand(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C) { return expand_as<false>(M, g, priors, A, C, nullptr); }
     // NOISE: when the leaf is node 0, P' = (1 - epsilon) P + epsilon eta (tafl_root_noise): the raw variates wait in the fresh edges' q
-    // between the two passes
+    // between the two passes (mix == false: this search takes no noise - a fast move of a capped run)
     template <bool NOISE>
-    static TAFL_HD bool expand_as(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C, const RootNoise* nz) {
+    static TAFL_HD bool expand_as(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C, const RootNoise* nz, bool mix = true) {
         const uint32_t L = M.leaf[g];
         S st; IO::load_rec(M.node_state + ((size_t)L * M.G + g) * IO::QUADS, st);
         const uint32_t base = M.edge_top[g];
@@ -232,7 +247,7 @@ struct Guided {
             for (uint32_t i = 0; i < cnt; ++i) e[i].p = (e[i].p + 1.0) / s2;
         }
         if constexpr (NOISE) {
-            if (L == 0) {
+            if (L == 0 && mix) {
                 double s = 0.0;
                 for (uint32_t i = 0; i < cnt; ++i) { const double gm = noise_gamma(*nz, e[i].action); e[i].q = gm; s += gm; }
                 const double keep = 1.0 - nz->epsilon;
@@ -253,11 +268,11 @@ struct Guided {
                              const K& C, GuidedStats& gs, const RootNoise& nz) { step_as<true>(M, g, priors, value, A, c_puct, n_sims, C, gs, &nz); }
     template <bool NOISE>
     static TAFL_HD void step_as(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                                const K& C, GuidedStats& gs, const RootNoise* nz) {
+                                const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true) {
         if (M.fault[g]) { M.kind[g] = 3; return; }
         uint32_t sims = M.sims_done[g];
         if (M.kind[g] == 1) {
-            if (!priors || !expand_as<NOISE>(M, g, priors, A, C, nz)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
+            if (!priors || !expand_as<NOISE>(M, g, priors, A, C, nz, mix)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
             gs.predicts += 1;
             backup(M, g, M.leaf[g], -(double)value);              // return -v (mcts.py:102) into the callers
             ++sims; gs.sims += 1;
@@ -434,9 +449,14 @@ struct Guided {
                                                const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz) {
         selfplay_step_as<true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, &nz, &ep);
     }
-    template <bool NOISE, bool EPISODES>
+    // CAP: the round of a capped run (include/taflhip.h tafl_playout_cap).  The class of the move whose search is open at entry keeps the
+    // noise and the example to a full move and counts the move when it is made.  A fast move searches pc->fast_sims simulations: when its
+    // root is about to be expanded (the search has done nothing yet) its sims_done starts at n_sims - fast_sims, so that `step` and the
+    // test that the search is complete keep the run's uniform n_sims
+    template <bool NOISE, bool EPISODES, bool CAP = false>
     static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                                         const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep) {
+                                         const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep,
+                                         const PlayoutCap* pc = nullptr) {
         uint32_t md = sp.moves_done[g];
         if (md & kGspStopped) return;
         // EPISODES: the game id and the first move of the lane's open episode (rec.move_base is 0); they hold for the whole call, a new
@@ -449,9 +469,15 @@ struct Guided {
         // (only the first pass of the loop below expands a leaf, so the move number of the search that is open now serves the whole call)
         RootNoise mine;
         if constexpr (NOISE) { mine = *nz; mine.gid = gid; mine.move_no = EPISODES ? md - m0 : rec.move_base + md; }
+        // (CAP: likewise the class of that move; the second pass begins the next search with sims_done = 0 and ends at its unexpanded root)
+        bool full = true;
+        if constexpr (CAP) {
+            full = cap_is_full(*pc, gid, EPISODES ? md - m0 : rec.move_base + md);
+            if (!full && M.kind[g] == 1 && M.leaf[g] == 0u) M.sims_done[g] = n_sims - pc->fast_sims;      // (fast_sims <= n_sims: the begin checks it)
+        }
         // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
         for (;;) {
-            step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr);
+            step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full);
             if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
             if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
             const GNode h = M.hdr[g];
@@ -468,7 +494,7 @@ struct Guided {
             if (move_no < rec.temp_moves) pick = selfplay_pick(eb, h.n_legal, total, selfplay_rand(rec.sample_seed, gid, move_no));
             const GEdge pe = eb[pick];
             S st;
-            if (rec.ex.len) {                                                // (tafl_examples.hpp; a guided edge carries its action, unvisited edges lie in between)
+            if (rec.ex.len && full) {                                        // (tafl_examples.hpp; a guided edge carries its action, unvisited edges lie in between)
                 IO::load_soa(soa, M.G, g, st);
                 example_append<NL, W>(rec.ex, g, st, C.n, m, pe.action, move_no, [&](auto&& put) {
                     for (uint32_t i = 0; i < h.n_legal; ++i) if (eb[i].n != 0u) put(eb[i].action, eb[i].n);
@@ -478,6 +504,7 @@ struct Guided {
             IO::store_soa(soa, M.G, g, st);
             Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;
             sp.plays[(size_t)md * M.G + g] = O::to_play(mv);
+            if constexpr (CAP) TAFL_COUNT_ADD(&pc->counters[full ? CAP_FULL : CAP_FAST], 1);
             md += 1u;
             if constexpr (EPISODES) {
                 if (md >= sp.n_moves) { sp.moves_done[g] = md | kGspStopped; return; }      // the budget is used up: the episode stays open
@@ -487,6 +514,12 @@ struct Guided {
             init_game(M, g, st);
             priors = nullptr;
         }
+    }
+    // the capped rounds (tafl_gselfplay_set_playout_cap): plain or episodes, without or with root noise
+    template <bool NOISE, bool EPISODES>
+    static TAFL_HD void selfplay_step_capped(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                             const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz, const PlayoutCap& pc) {
+        selfplay_step_as<NOISE, EPISODES, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc);
     }
     // a fresh root that waits for its evaluation: what `step` leaves when it meets the unexpanded root of an ongoing game
     static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) { init_game(M, g, root); M.kind[g] = 1; }

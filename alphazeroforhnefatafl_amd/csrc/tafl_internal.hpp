@@ -238,6 +238,11 @@ struct tafl_batch {
     // Dirichlet noise at the root (tafl_gmcts_set_root_noise): the setting, and what the open search or run latched at its begin
     bool noise_set = false, g_noise_on = false;
     tafl_root_noise noise_cfg = {}; RootNoise g_noise = {};
+    // playout cap randomization (tafl_gselfplay_set_playout_cap): the setting, and what the guided self-play run that is open, or was last,
+    // latched at its begin (gsp_cap_on: it is a capped run; its two class counters)
+    bool cap_set = false, gsp_cap_on = false;
+    tafl_playout_cap cap_cfg = {}; PlayoutCap gsp_cap = {};
+    DevBuf gsp_cap_counters;
     // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
     // arena and the id map of a re-root; a small read-back buffer
     bool tree_live = false, g_tree_live = false;

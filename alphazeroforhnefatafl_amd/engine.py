@@ -13,8 +13,14 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
+
+
+def full_per_65536(full_prob: float) -> int:
+    """tafl_playout_cap.full_per_65536 for the probability `full_prob` of a full move: round(full_prob * 65536)."""
+    return int(round(full_prob * 65536))
+
 
 KC_MOVEGEN, KC_STEP, KC_ROLLOUT, KC_MCTS_TREE, KC_MCTS_ROLLOUT = range(5)
 
@@ -444,6 +450,23 @@ class GameBatch:
 
     def clear_root_noise(self):
         check(lib().tafl_gmcts_set_root_noise(self._h, None))
+
+    # -- playout cap randomization of a guided self-play run (include/taflhip.h tafl_playout_cap) ------------------------------
+    def set_playout_cap(self, fast_sims: int, full_prob: float, seed: int = 0):
+        """Every later gselfplay_begin / gselfplay_begin_episodes run (latched at the begin) searches a move at full strength - n_sims
+        simulations, root noise if set, the example recorded - with probability round(full_prob * 65536) / 65536 and otherwise with
+        `fast_sims` simulations, no noise and no example; the class is a function of (seed, game id, move number)."""
+        cfg = TaflPlayoutCap(seed, fast_sims, full_per_65536(full_prob), 0)
+        check(lib().tafl_gselfplay_set_playout_cap(self._h, C.byref(cfg)))
+
+    def clear_playout_cap(self):
+        check(lib().tafl_gselfplay_set_playout_cap(self._h, None))
+
+    def playout_cap_stats(self) -> TaflPlayoutCapStats:
+        """The moves the capped run that is open, or was last, made per class (tafl_gselfplay_playout_cap_stats)."""
+        st = TaflPlayoutCapStats()
+        check(lib().tafl_gselfplay_playout_cap_stats(self._h, C.byref(st)))
+        return st
 
     def root_noise_eval(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0, out_device_ptr: int | None = None):
         """eta of tafl_root_noise_eval for every game's current state: float64 [n * action_size], zero off the legal actions."""

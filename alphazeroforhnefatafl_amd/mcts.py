@@ -14,7 +14,7 @@ from __future__ import annotations
 
 from dataclasses import dataclass
 
-from .engine import GameBatch
+from .engine import GameBatch, full_per_65536  # noqa: F401
 
 
 @dataclass
@@ -29,6 +29,11 @@ class MCTSArgs:
     dirichletAlpha: float = 0.0
     dirichletEpsilon: float = 0.0
     noiseSeed: int = 0
+    # playout cap randomization of a guided self-play run (include/taflhip.h tafl_playout_cap); fastSims 0: off.  A move is searched with
+    # numMCTSSims simulations and recorded with probability fullMoveProb, otherwise with fastSims simulations and not recorded.
+    fastSims: int = 0
+    fullMoveProb: float = 1.0
+    capSeed: int = 0
 
 
 def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
@@ -37,6 +42,34 @@ def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
         batch.set_root_noise(args.dirichletAlpha, args.dirichletEpsilon, args.noiseSeed, args.game_id_base, move_no)
     else:
         batch.clear_root_noise()
+
+
+def apply_playout_cap(batch: GameBatch, args: MCTSArgs):
+    """The batch's playout-cap setting as `args` asks for it: set, or cleared when fastSims is 0."""
+    if args.fastSims:
+        batch.set_playout_cap(args.fastSims, args.fullMoveProb, args.capSeed)
+    else:
+        batch.clear_playout_cap()
+
+
+_M32 = 0xFFFFFFFF
+
+
+def _fmix32(h):
+    h &= _M32; h ^= h >> 16; h = (h * 0x85EBCA6B) & _M32; h ^= h >> 13; h = (h * 0xC2B2AE35) & _M32; h ^= h >> 16
+    return h
+
+
+def playout_cap_is_full(seed: int, gid: int, move_no: int, full_per_65536: int) -> bool:
+    """Whether move `move_no` of game `gid` is a full move under a playout cap with `seed` (include/taflhip.h tafl_playout_cap, the rule
+    restated in Python): what a host needs to tell which plays of a capped run were searched at full strength and recorded."""
+    f = _fmix32
+    slo, shi, glo, ghi = seed & _M32, (seed >> 32) & _M32, gid & _M32, (gid >> 32) & _M32
+    h0, h1 = f(slo ^ f(shi + 0x9E3779B9)), f(shi ^ f(slo + 0x7F4A7C15))
+    lo, hi = f(f(h0 ^ glo) + ghi), f(f(h1 ^ ghi) + glo * 0x9E3779B1)                      # game_key(seed, gid)
+    lo, hi = lo ^ 0x4F555443, hi ^ 0x504C4159                                            # ^ 0x504C41594F555443
+    sk = f(lo ^ ((move_no * 0x9E3779B1 + 0x7F4A7C15) & _M32)) ^ f((hi + move_no * 0x85EBCA77 + 0x165667B1) & _M32)   # sim_key(.., M)
+    return (f(sk) >> 16) < full_per_65536                                                # ply_rand(.., 0) >> 16
 
 
 class MCTS:

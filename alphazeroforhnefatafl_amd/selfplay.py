@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi import TaflState
 from .engine import Examples, GameBatch
-from .mcts import MCTSArgs, apply_root_noise
+from .mcts import MCTSArgs, apply_playout_cap, apply_root_noise
 
 
 class MatchResult:
@@ -47,8 +47,11 @@ def play_match(batch: GameBatch, nets, args: MCTSArgs, lane_moves: int, *, examp
     must be 0: a match takes no root noise."""
     if args.dirichletEpsilon:
         raise ValueError("play_match: a match takes no root noise (args.dirichletEpsilon must be 0)")
+    if args.fastSims:
+        raise ValueError("play_match: a match takes no playout cap (args.fastSims must be 0)")
     n = batch.n
     batch.clear_root_noise()
+    batch.clear_playout_cap()
     batch.gmatch_begin(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                        temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings, swap=swap)
     ptrs = None
@@ -110,8 +113,11 @@ def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     (tafl_gselfplay_*): every game searches args.numMCTSSims simulations per move at its own pace, so the host loop is leaves -> network
     -> step until nothing waits, with no read-back per move.  Ends with Examples.finalize.  Returns (examples per game, their sum,
     games that are over).  args.dirichletEpsilon > 0 mixes Dirichlet(args.dirichletAlpha) noise into every root's priors
-    (include/taflhip.h tafl_root_noise), keyed by args.noiseSeed, the game id and the move number `move_base` + moves made."""
+    (include/taflhip.h tafl_root_noise), keyed by args.noiseSeed, the game id and the move number `move_base` + moves made.
+    args.fastSims > 0 turns on playout cap randomization (include/taflhip.h tafl_playout_cap): a move is full - args.numMCTSSims
+    simulations, noise, recorded - with probability args.fullMoveProb, otherwise args.fastSims simulations, no noise, not recorded."""
     apply_root_noise(batch, args)
+    apply_playout_cap(batch, args)
     batch.gselfplay_begin(examples, max_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=args.game_id_base,
                           sample_seed=sample_seed, temp_moves=temp_moves, move_base=move_base)
     waiting = batch.gselfplay_step()
@@ -137,9 +143,11 @@ def play_guided_selfplay(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     in the same round, so the evaluator's batch stays full.  Episode k of lane g has the game id game_id_base + k * id_stride + g
     (id_stride 0: the batch size; a sharded caller passes the total).  The loop is leaves -> network -> step until nothing waits
     (nnet, device and buffers as in play_guided_episodes); then Examples.finalize settles the open tails.  args.dirichletEpsilon > 0
-    mixes root noise keyed by the episode's game id and move number.  Returns (episodes closed or cut per lane, TaflEpisodeStats,
-    examples recorded in all, (dropped, overflowed))."""
+    mixes root noise keyed by the episode's game id and move number; args.fastSims > 0 turns on playout cap randomization as in
+    play_guided_episodes (mcts.playout_cap_is_full tells which moves were full; batch.playout_cap_stats() counts them).  Returns
+    (episodes closed or cut per lane, TaflEpisodeStats, examples recorded in all, (dropped, overflowed))."""
     apply_root_noise(batch, args)
+    apply_playout_cap(batch, args)
     batch.gselfplay_begin_episodes(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                                    temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings)
     waiting = batch.gselfplay_step()

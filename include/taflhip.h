@@ -593,7 +593,8 @@ int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves)
  *   capacity      `ex` holds max_moves examples per LANE, over all its episodes; dropped and overflowed are counted as before.
  * tafl_examples_finalize writes only the examples from open_from[g] on.  open_from is zero at tafl_examples_create and after
  *   tafl_examples_clear and only an episodes run moves it, so for an object that never saw one the call writes what it always wrote.
- *   tafl_examples_gather, _read and _counts are unchanged; an episode boundary in a lane's column is where move_no returns to 0.
+ *   tafl_examples_gather, _read and _counts are unchanged; an episode boundary in a lane's column is where move_no returns to 0 (in a run
+ *   without a playout cap; with one, see tafl_playout_cap: move_no alone no longer shows it).
  * tafl_gselfplay_episode_stats: out_episodes[n] (may be NULL) = the episodes of each lane that were closed or cut, and the counters; valid
  *   from the begin until the next tafl_gselfplay_begin / _begin_episodes on the batch (TAFL_ERR_INVALID_ARG without an episodes run).
  * Non-zero eo->flags or reserved words: TAFL_ERR_UNSUPPORTED; eo == NULL: TAFL_ERR_INVALID_ARG; everything tafl_gselfplay_begin rejects is
@@ -729,6 +730,51 @@ typedef struct tafl_root_noise {
 int tafl_gmcts_set_root_noise(tafl_batch* b, const tafl_root_noise* cfg);
 int tafl_root_noise_eval(tafl_batch* b, const tafl_root_noise* cfg, double* out_eta, int out_is_device);
 int tafl_gmcts_root_priors(tafl_batch* b, double* out, int out_is_device);
+
+/* ---- playout cap randomization in guided self-play ----------------------------------------------------------------
+ * Most moves of a tafl_gselfplay run are searched cheaply, only to keep the game moving; a random minority is searched at full strength
+ * and only those become training examples (KataGo's playout cap randomization).  Build-defined.  Off by default; with it off nothing in
+ * this header behaves differently.  A lane whose move is fast finishes its search in fewer rounds and moves on inside the same launches.
+ *
+ * Let gid and M be the game id and the move number the run already uses for the word that draws a play and for the root-noise key: in a
+ * plain run game_id_base + g and opts->move_base + the moves game g has made in the run, in an episodes run those of the lane's open
+ * episode (game_id_base + k * id_stride + g and the moves that episode has made).
+ *   class      w = ply_rand(sim_key(game_key(seed, gid) ^ 0x504C41594F555443, M), 0)  (the taflmix32 family; the constant keeps the stream
+ *              apart from the sample stream and the noise stream when the seeds are equal).  The move is FULL iff (w >> 16) < full_per_65536,
+ *              otherwise FAST: a pure function of (seed, gid, M), not of the lane, the sharding or what the run has done before.
+ *              full_per_65536 = 65536 makes every move full, 0 makes every move fast.
+ *   full move  the move as it is without a cap: n_sims simulations from a fresh root, root noise if the run latched it, the example is
+ *              appended.
+ *   fast move  fast_sims simulations from a fresh root.  No root noise, even when the run latched it.  No example is appended: len[g], the
+ *              dropped and the overflowed counter are untouched.
+ *   both       the play is chosen by the run's rule - for M < temp_moves the draw with the sample word of (gid, M), otherwise the most
+ *              visited root edge, first maximum - and made on the batch state.  plays[m * n + g], out_moves, the lane budget,
+ *              episode_moves, closing, cutting and reopening are unchanged: a fast move counts as a move everywhere.
+ *   move_no    a recorded example keeps move_no = M.  Within an episode the recorded numbers increase but have gaps, and an episode may
+ *              close having recorded nothing (then open_from[g] stays equal to len[g]).  With a cap an episode boundary in a lane's column
+ *              can therefore NOT be read from move_no alone (it need not return to 0): use open_from, z / final and the episode counts.
+ *   stats      tafl_gmcts_stats.sims counts the simulations actually run (n_sims per full move, fast_sims per fast one when nothing faults).
+ *
+ * tafl_gselfplay_set_playout_cap stores the setting on the batch (cfg == NULL: off).  tafl_gselfplay_begin and
+ *   tafl_gselfplay_begin_episodes latch it: a change during a run takes effect at the next begin.  fast_sims < 2, fast_sims > 65535 or
+ *   full_per_65536 > 65536: TAFL_ERR_INVALID_ARG; non-zero flags or _reserved: TAFL_ERR_UNSUPPORTED (in both cases the setting is left as
+ *   it was).  A begin with fast_sims > n_sims fails with TAFL_ERR_INVALID_ARG and leaves no run open, so the arena stays sized by n_sims.
+ *   While a cap is set tafl_gmatch_begin fails with TAFL_ERR_UNSUPPORTED.  The lock-step tafl_gmcts_* searches and the rollout-mode
+ *   tafl_selfplay_record ignore the setting.
+ * tafl_gselfplay_playout_cap_stats: the moves made per class, counted on the device when the move is made; valid from the begin until
+ *   the next tafl_gselfplay_begin / _begin_episodes on the batch (also after tafl_gselfplay_end), TAFL_ERR_INVALID_ARG when that run
+ *   latched no cap.
+ * Not offered: recording fast moves, a cap in match runs or in rollout-mode self-play, subtree reuse (every move starts from a fresh root). */
+typedef struct tafl_playout_cap {
+    uint64_t seed;
+    uint32_t fast_sims;        /* 2 .. n_sims of the run */
+    uint32_t full_per_65536;   /* 0 .. 65536: a move is full with probability full_per_65536 / 65536 */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[3];     /* 0 */
+} tafl_playout_cap;            /* 32 bytes */
+typedef struct tafl_playout_cap_stats { uint64_t full_moves, fast_moves, _reserved[2]; } tafl_playout_cap_stats;   /* 32 bytes */
+int tafl_gselfplay_set_playout_cap(tafl_batch* b, const tafl_playout_cap* cfg);
+int tafl_gselfplay_playout_cap_stats(tafl_batch* b, tafl_playout_cap_stats* out);
 
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
