@@ -174,6 +174,16 @@ class TaflPlayoutCapStats(C.Structure):
     _fields_ = [("full_moves", C.c_uint64), ("fast_moves", C.c_uint64), ("_reserved", C.c_uint64 * 2)]
 
 
+class TaflForcedPlayouts(C.Structure):
+    """tafl_forced_playouts: forced playouts and policy target pruning of a guided self-play run (tafl_gselfplay_set_forced_playouts)."""
+    _fields_ = [("k", C.c_double), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 5)]
+
+
+class TaflForcedPlayoutsStats(C.Structure):
+    """tafl_forced_playouts_stats: what a run with forced playouts forced and pruned."""
+    _fields_ = [("forced_sims", C.c_uint64), ("pruned_visits", C.c_uint64), ("pruned_children", C.c_uint64), ("full_moves", C.c_uint64)]
+
+
 class TaflEpisodeOpts(C.Structure):
     """tafl_episode_opts: a guided self-play run in episodes (tafl_gselfplay_begin_episodes)."""
     _fields_ = [("id_stride", C.c_uint64), ("episode_moves", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
@@ -209,7 +219,8 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
                   "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
                   "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64, "tafl_match_opts": 32, "tafl_match_io": 72,
-                  "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32}
+                  "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
+                  "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -217,7 +228,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_selfplay_opts", TaflSelfplayOpts), ("tafl_examples_stats", TaflExamplesStats),
                     ("tafl_root_noise", TaflRootNoise), ("tafl_episode_opts", TaflEpisodeOpts),
                     ("tafl_episode_stats", TaflEpisodeStats), ("tafl_match_opts", TaflMatchOpts), ("tafl_match_io", TaflMatchIo),
-                    ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats)]:
+                    ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats),
+                    ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

@@ -210,6 +210,19 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_capped(Consts<NL> C, G
                                                                   gs, nz, pc);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+// the round of a run with forced playouts (tafl_gselfplay_set_forced_playouts), again kernels of their own.  They
+// go through the capped path: a run without a cap passes a PlayoutCap under which every move is full
+template <int NL, int W, bool NOISE, bool EPISODES>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_forced(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                                 uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats, RootNoise nz, PlayoutCap pc,
+                                                                 ForcedPlayouts fp) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::template selfplay_step_forced<NOISE, EPISODES>(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C,
+                                                                  gs, nz, pc, fp);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
 // close and reopen, right after the round on the same stream: the lanes whose episode ended settle its examples, count it, take their
 // opening and wait with a fresh root (Guided::selfplay_reopen); every other lane leaves at its first load
 template <int NL, int W>
@@ -384,7 +397,35 @@ static int cap_check(const tafl_playout_cap* cfg) {
     return TAFL_OK;
 }
 
+// a tafl_forced_playouts the library accepts
+static int forced_check(const tafl_forced_playouts* cfg) {
+    if (!(cfg->k > 0.0) || !(cfg->k <= 64.0)) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_forced_playouts: k must be finite, above 0 and at most 64");
+    if (cfg->flags != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_forced_playouts: flags and reserved words must be 0");
+    for (uint32_t r : cfg->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_forced_playouts: flags and reserved words must be 0");
+    return TAFL_OK;
+}
+
 extern "C" {
+
+int tafl_gselfplay_set_forced_playouts(tafl_batch* b, const tafl_forced_playouts* cfg) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_forced_playouts: null batch");
+    if (!cfg) { b->forced_set = false; return TAFL_OK; }
+    if (const int rc = forced_check(cfg)) return rc;
+    b->forced_set = true; b->forced_cfg = *cfg;
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_forced_playouts_stats(tafl_batch* b, tafl_forced_playouts_stats* out) {
+    if (!b || !b->gsp_has || !b->gsp_forced_on || !out)
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_forced_playouts_stats: no run with forced playouts on this batch (tafl_gselfplay_set_forced_playouts, then a begin)");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[FP_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->gsp_forced_counters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out->forced_sims = h[FP_FORCED_SIMS]; out->pruned_visits = h[FP_PRUNED_VISITS]; out->pruned_children = h[FP_PRUNED_CHILDREN]; out->full_moves = h[FP_FULL_MOVES];
+    return TAFL_OK;
+}
 
 int tafl_gselfplay_set_playout_cap(tafl_batch* b, const tafl_playout_cap* cfg) {
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_playout_cap: null batch");
@@ -609,7 +650,18 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    if (b->gsp_cap_on) {                                        // a capped run: rounds of its own, then the reopen of an episodes run as below
+    if (b->gsp_forced_on) {                                     // forced playouts: rounds of their own (with or without a cap), then the reopen
+        const bool nz = b->g_noise_on, ep = b->gsp_episodes;
+#define TAFL_FORCED(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_forced<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap, b->gsp_forced); })
+        if (ep) { if (nz) TAFL_FORCED(true, true); else TAFL_FORCED(false, true); }
+        else { if (nz) TAFL_FORCED(true, false); else TAFL_FORCED(false, false); }
+#undef TAFL_FORCED
+        if (ep) {
+            HIPCHK(hipGetLastError());
+            dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+        }
+    }
+    else if (b->gsp_cap_on) {                                   // a capped run: rounds of its own, then the reopen of an episodes run as below
         const bool nz = b->g_noise_on, ep = b->gsp_episodes;
 #define TAFL_CAPPED(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_capped<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap); })
         if (ep) { if (nz) TAFL_CAPPED(true, true); else TAFL_CAPPED(false, true); }
@@ -684,11 +736,19 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     b->g_noise_on = b->noise_set;                            // the run latches the noise setting; gid and M are the run's own
     if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     b->gsp_cap_on = b->cap_set; b->gsp_cap = PlayoutCap{};   // and the playout cap
-    if (b->cap_set) {
+    b->gsp_forced_on = b->forced_set; b->gsp_forced = ForcedPlayouts{};      // and forced playouts, whose rounds take a PlayoutCap in any case
+    if (b->cap_set || b->forced_set) {
         NEED(b->gsp_cap_counters, sizeof(unsigned long long) * CAP_COUNT);
         HIPCHK(hipMemsetAsync(b->gsp_cap_counters.p, 0, sizeof(unsigned long long) * CAP_COUNT, c->stream));
-        b->gsp_cap.seed = b->cap_cfg.seed; b->gsp_cap.fast_sims = b->cap_cfg.fast_sims; b->gsp_cap.full_per_65536 = b->cap_cfg.full_per_65536;
+        if (b->cap_set) { b->gsp_cap.seed = b->cap_cfg.seed; b->gsp_cap.fast_sims = b->cap_cfg.fast_sims; b->gsp_cap.full_per_65536 = b->cap_cfg.full_per_65536; }
+        else { b->gsp_cap.fast_sims = n_sims; b->gsp_cap.full_per_65536 = 65536u; }      // (every move is full)
         b->gsp_cap_counters.bind(b->gsp_cap.counters);
+    }
+    if (b->forced_set) {
+        NEED(b->gsp_forced_counters, sizeof(unsigned long long) * FP_COUNT);
+        HIPCHK(hipMemsetAsync(b->gsp_forced_counters.p, 0, sizeof(unsigned long long) * FP_COUNT, c->stream));
+        b->gsp_forced.k = b->forced_cfg.k;
+        b->gsp_forced_counters.bind(b->gsp_forced.counters);
     }
     HIPCHK(hipMemsetAsync(b->gsp_plays.p, 0, sizeof(tafl_play) * (size_t)n * n_moves, c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_init<t.NL, t.W>), c, n, t.CC, b->soa, b->gmem, b->gsp); });
@@ -756,6 +816,7 @@ int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, d
     for (uint32_t r : mo->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
     if (b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: root noise is set on the batch (tafl_gmcts_set_root_noise(NULL) first)");
     if (b->cap_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: a playout cap is set on the batch (tafl_gselfplay_set_playout_cap(NULL) first)");
+    if (b->forced_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: forced playouts are set on the batch (tafl_gselfplay_set_forced_playouts(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     if (const int rc = gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b)) return rc;
     b->gsp_active = false; b->gsp_has = false;                 // (the run counts as open once its match buffers exist)

@@ -96,6 +96,12 @@ static TAFL_HD bool cap_is_full(const PlayoutCap& pc, uint64_t gid, uint32_t mov
     using E = Engine<2, 7>;
     return (E::ply_rand(E::sim_key(E::game_key(pc.seed, gid) ^ kCapKey, move_no), 0u) >> 16) < pc.full_per_65536;
 }
+// forced playouts and policy target pruning (include/taflhip.h tafl_forced_playouts): an argument of the forced rounds alone
+enum { FP_FORCED_SIMS = 0, FP_PRUNED_VISITS, FP_PRUNED_CHILDREN, FP_FULL_MOVES, FP_COUNT };
+struct ForcedPlayouts {
+    double k;                       // a visited root edge is forced while n * n < (k * p) * Ns
+    unsigned long long* counters;   // [FP_COUNT]
+};
 // Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
 struct RootNoise {
     double alpha, epsilon;
@@ -266,9 +272,11 @@ struct Guided {
     // the round with the root noise `nz` of this game's search
     static TAFL_HD void step(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                              const K& C, GuidedStats& gs, const RootNoise& nz) { step_as<true>(M, g, priors, value, A, c_puct, n_sims, C, gs, &nz); }
-    template <bool NOISE>
+    // FORCED (the forced rounds, include/taflhip.h tafl_forced_playouts rule 1): in the search of a full move (`mix`) a visited edge of
+    // node 0 with n * n < (k * p) * Ns scores +inf, so the first such edge is selected; *forced counts the simulations this happened to
+    template <bool NOISE, bool FORCED = false>
     static TAFL_HD void step_as(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                                const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true) {
+                                const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true, const ForcedPlayouts* fp = nullptr, uint32_t* forced = nullptr) {
         if (M.fault[g]) { M.kind[g] = 3; return; }
         uint32_t sims = M.sims_done[g];
         if (M.kind[g] == 1) {
@@ -288,16 +296,20 @@ struct Guided {
                 GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
                 const double sq = sqrt((double)h.ns), sq0 = sqrt((double)h.ns + TAFL_MCTS_EPS);
                 double cur_best = -__builtin_inf(); int best = -1;
+                bool force = false; double kns = 0.0;
+                if constexpr (FORCED) { force = mix && cur == 0u; kns = (double)h.ns; }
                 // eight edge records in flight at a time (the scan is bound by memory latency), evaluated in ascending action order
                 for (uint32_t j0 = 0; j0 < h.n_legal; j0 += 8) {
                     double ep[8], eq[8]; uint32_t en[8];
                     TAFL_UNROLL for (uint32_t t = 0; t < 8; ++t) { const GEdge* e = &eb[(j0 + t < h.n_legal) ? j0 + t : j0]; ep[t] = e->p; eq[t] = e->q; en[t] = e->n; }
                     TAFL_UNROLL for (uint32_t t = 0; t < 8; ++t) {
-                        const double u = en[t] > 0 ? eq[t] + c_puct * ep[t] * sq / (double)(1 + en[t]) : c_puct * ep[t] * sq0;
+                        double u = en[t] > 0 ? eq[t] + c_puct * ep[t] * sq / (double)(1 + en[t]) : c_puct * ep[t] * sq0;
+                        if constexpr (FORCED) { if (force && en[t] > 0 && (double)en[t] * (double)en[t] < (fp->k * ep[t]) * kns) u = __builtin_inf(); }
                         if (j0 + t < h.n_legal && u > cur_best) { cur_best = u; best = (int)(j0 + t); }
                     }
                 }
                 if (best < 0) { M.fault[g] = 1; gs.faults += 1; M.sims_done[g] = sims; return; }
+                if constexpr (FORCED) { if (force && cur_best == __builtin_inf()) *forced += 1u; }
                 uint32_t child = eb[best].child;
                 if (child == 0) {                                     // getNextState (mcts.py:122-123): first visit of this edge
                     const uint32_t id = M.node_top[g];
@@ -415,6 +427,33 @@ struct Guided {
     }
 
     // ---- guided self-play at each game's own pace (tafl_gselfplay_*) -----------------------------------------
+    // Policy target pruning (include/taflhip.h tafl_forced_playouts rule 2) of the finished root `h` of a full move, in place: every
+    // visited edge but the first most visited one gives back up to F visits, one at a time, while its PUCT value with one visit fewer
+    // stays below that of the most visited edge; an edge pruned to a single visit is pruned to none.  Counts what it took away.
+    static TAFL_HD void forced_prune(GEdge* eb, const GNode& h, double c_puct, const ForcedPlayouts& fp) {
+        uint32_t best = 0, b = 0;
+        for (uint32_t j = 0; j < h.n_legal; ++j) { const uint32_t v = eb[j].n; if (v > best) { best = v; b = j; } }
+        if (best == 0u) return;
+        const double ns = (double)h.ns, sq = sqrt(ns);
+        const double ustar = eb[b].q + c_puct * eb[b].p * sq / (double)(1 + eb[b].n);
+        uint32_t visits = 0, children = 0;
+        for (uint32_t j = 0; j < h.n_legal; ++j) {
+            const uint32_t nj = eb[j].n;
+            if (nj == 0u || j == b) continue;
+            const double p = eb[j].p, q = eb[j].q, x = (fp.k * p) * ns;
+            uint32_t F = (uint32_t)sqrt(x);                           // sqrt(x) rounded up, decided by the integer comparison
+            while ((double)F * (double)F < x) ++F;
+            while (F > 0u && (double)(F - 1u) * (double)(F - 1u) >= x) --F;
+            uint32_t m = nj;
+            for (uint32_t i = 0; i < F && m != 0u; ++i) {
+                if (q + c_puct * p * sq / (double)(1 + (m - 1u)) < ustar) m -= 1u; else break;
+            }
+            if (m < nj && m <= 1u) m = 0u;
+            if (m != nj) { eb[j].n = m; visits += nj - m; children += m == 0u; }
+        }
+        if (visits) TAFL_COUNT_ADD(&fp.counters[FP_PRUNED_VISITS], visits);
+        if (children) TAFL_COUNT_ADD(&fp.counters[FP_PRUNED_CHILDREN], children);
+    }
     // visit_draw (tafl_examples.hpp) over the root's edge block (one edge per LEGAL move, the unvisited ones in between): the index inside the block
     static TAFL_HD uint32_t selfplay_pick(const GEdge* eb, uint32_t n_legal, uint32_t N, uint32_t r) { return visit_draw(n_legal, N, r, [&](uint32_t j) { return eb[j].n; }); }
     // the start of a run for game g: a fresh root from its batch state; a game that is over makes no move
@@ -453,10 +492,13 @@ struct Guided {
     // noise and the example to a full move and counts the move when it is made.  A fast move searches pc->fast_sims simulations: when its
     // root is about to be expanded (the search has done nothing yet) its sims_done starts at n_sims - fast_sims, so that `step` and the
     // test that the search is complete keep the run's uniform n_sims
-    template <bool NOISE, bool EPISODES, bool CAP = false>
+    // FORCED: the round of a run with forced playouts (include/taflhip.h tafl_forced_playouts).  The search of a full move forces at
+    // the root (step_as); when it is complete the visit counts of the root's edges are pruned in place (forced_prune: the block is dead
+    // once the move is made), so the scan, the draw and the example below read n' as they read n
+    template <bool NOISE, bool EPISODES, bool CAP = false, bool FORCED = false>
     static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                          const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep,
-                                         const PlayoutCap* pc = nullptr) {
+                                         const PlayoutCap* pc = nullptr, const ForcedPlayouts* fp = nullptr) {
         uint32_t md = sp.moves_done[g];
         if (md & kGspStopped) return;
         // EPISODES: the game id and the first move of the lane's open episode (rec.move_base is 0); they hold for the whole call, a new
@@ -477,10 +519,15 @@ struct Guided {
         }
         // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
         for (;;) {
-            step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full);
+            if constexpr (FORCED) {
+                uint32_t forced = 0;
+                step_as<NOISE, true>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced);
+                if (forced) TAFL_COUNT_ADD(&fp->counters[FP_FORCED_SIMS], forced);
+            } else step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full);
             if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
             if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
             const GNode h = M.hdr[g];
+            if constexpr (FORCED) { if (full && h.expanded) forced_prune(&M.edges[(size_t)g * M.edge_cap + h.edge_base], h, c_puct, *fp); }
             const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
             uint32_t best = 0, pick = 0, total = 0, m = 0;
             if (h.expanded)
@@ -505,6 +552,7 @@ struct Guided {
             Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;
             sp.plays[(size_t)md * M.G + g] = O::to_play(mv);
             if constexpr (CAP) TAFL_COUNT_ADD(&pc->counters[full ? CAP_FULL : CAP_FAST], 1);
+            if constexpr (FORCED) { if (full) TAFL_COUNT_ADD(&fp->counters[FP_FULL_MOVES], 1); }
             md += 1u;
             if constexpr (EPISODES) {
                 if (md >= sp.n_moves) { sp.moves_done[g] = md | kGspStopped; return; }      // the budget is used up: the episode stays open
@@ -520,6 +568,13 @@ struct Guided {
     static TAFL_HD void selfplay_step_capped(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                              const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz, const PlayoutCap& pc) {
         selfplay_step_as<NOISE, EPISODES, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc);
+    }
+    // the forced rounds (tafl_gselfplay_set_forced_playouts): always through the capped path - a run without a cap passes "every move full"
+    template <bool NOISE, bool EPISODES>
+    static TAFL_HD void selfplay_step_forced(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                             const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz, const PlayoutCap& pc,
+                                             const ForcedPlayouts& fp) {
+        selfplay_step_as<NOISE, EPISODES, true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc, &fp);
     }
     // a fresh root that waits for its evaluation: what `step` leaves when it meets the unexpanded root of an ongoing game
     static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) { init_game(M, g, root); M.kind[g] = 1; }

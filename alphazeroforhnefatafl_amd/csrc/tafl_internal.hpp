@@ -243,6 +243,11 @@ struct tafl_batch {
     bool cap_set = false, gsp_cap_on = false;
     tafl_playout_cap cap_cfg = {}; PlayoutCap gsp_cap = {};
     DevBuf gsp_cap_counters;
+    // forced playouts and policy target pruning (tafl_gselfplay_set_forced_playouts): the setting, and what that run latched (gsp_forced_on:
+    // its rounds are the forced ones; its four counters)
+    bool forced_set = false, gsp_forced_on = false;
+    tafl_forced_playouts forced_cfg = {}; ForcedPlayouts gsp_forced = {};
+    DevBuf gsp_forced_counters;
     // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
     // arena and the id map of a re-root; a small read-back buffer
     bool tree_live = false, g_tree_live = false;

@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -466,6 +466,24 @@ class GameBatch:
         """The moves the capped run that is open, or was last, made per class (tafl_gselfplay_playout_cap_stats)."""
         st = TaflPlayoutCapStats()
         check(lib().tafl_gselfplay_playout_cap_stats(self._h, C.byref(st)))
+        return st
+
+    # -- forced playouts and policy target pruning of a guided self-play run (include/taflhip.h tafl_forced_playouts) -----------
+    def set_forced_playouts(self, k: float):
+        """Every later gselfplay_begin / gselfplay_begin_episodes run (latched at the begin) forces, in the search of a full move, each
+        visited root child to at least sqrt(k * p * Ns) visits and prunes the visits the search did not confirm from what it draws the
+        play from and records."""
+        cfg = TaflForcedPlayouts(k, 0)
+        check(lib().tafl_gselfplay_set_forced_playouts(self._h, C.byref(cfg)))
+
+    def clear_forced_playouts(self):
+        check(lib().tafl_gselfplay_set_forced_playouts(self._h, None))
+
+    def forced_playouts_stats(self) -> TaflForcedPlayoutsStats:
+        """Forced simulations, pruned visits, pruned children and full moves of the run that is open, or was last
+        (tafl_gselfplay_forced_playouts_stats)."""
+        st = TaflForcedPlayoutsStats()
+        check(lib().tafl_gselfplay_forced_playouts_stats(self._h, C.byref(st)))
         return st
 
     def root_noise_eval(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0, out_device_ptr: int | None = None):

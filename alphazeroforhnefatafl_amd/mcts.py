@@ -34,6 +34,8 @@ class MCTSArgs:
     fastSims: int = 0
     fullMoveProb: float = 1.0
     capSeed: int = 0
+    # forced playouts and policy target pruning of a guided self-play run (include/taflhip.h tafl_forced_playouts); 0: off
+    forcedPlayoutsK: float = 0.0
 
 
 def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
@@ -50,6 +52,14 @@ def apply_playout_cap(batch: GameBatch, args: MCTSArgs):
         batch.set_playout_cap(args.fastSims, args.fullMoveProb, args.capSeed)
     else:
         batch.clear_playout_cap()
+
+
+def apply_forced_playouts(batch: GameBatch, args: MCTSArgs):
+    """The batch's forced-playouts setting as `args` asks for it: set, or cleared when forcedPlayoutsK is 0."""
+    if args.forcedPlayoutsK:
+        batch.set_forced_playouts(args.forcedPlayoutsK)
+    else:
+        batch.clear_forced_playouts()
 
 
 _M32 = 0xFFFFFFFF

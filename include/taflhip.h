@@ -776,6 +776,49 @@ typedef struct tafl_playout_cap_stats { uint64_t full_moves, fast_moves, _reserv
 int tafl_gselfplay_set_playout_cap(tafl_batch* b, const tafl_playout_cap* cfg);
 int tafl_gselfplay_playout_cap_stats(tafl_batch* b, tafl_playout_cap_stats* out);
 
+/* ---- forced playouts and policy target pruning in guided self-play ---------------------------------------------------
+ * Root noise only changes priors: with few simulations a move the noise likes gets a visit or two and is never tested.  Forcing gives
+ * every visited root child a minimum number of visits that grows with its (noised) prior; pruning then takes those visits out of the
+ * recorded policy target wherever the search did not confirm them (KataGo's forced playouts with policy target pruning).  Build-defined.
+ * Off by default; with it off nothing in this header behaves differently.
+ *
+ * All arithmetic is float64, in the order written, without contraction.  p, q, n are the fields of a root edge (Ps, Qsa, Nsa; for a move
+ * that takes root noise p is the mixed prior), ns is the root's Ns, c_puct the run's.
+ *   1 forcing   only at node 0 and only in the search of a FULL move (without a playout cap every move is full; a fast move of a capped
+ *               run is neither forced nor pruned, as it takes no noise).  In the selection scan an edge with n > 0 and
+ *               (double)n * (double)n < (k * p) * (double)ns scores +inf instead of its PUCT value.  The scan keeps its ascending action
+ *               order and its strict >, so the first such edge is selected.  Every other node and edge keeps its arithmetic bit for bit.
+ *   2 pruning   when the search of a full move is complete, before the play is chosen.  b = the first most visited root edge.
+ *               sq = sqrt((double)ns);  U* = q_b + c_puct * p_b * sq / (double)(1 + n_b).  For every other visited edge j:
+ *                 x = (k * p_j) * (double)ns;  F_j = the smallest integer F >= 0 with (double)F * (double)F >= x;
+ *                 m = n_j; at most F_j times: stop if m == 0; if q_j + c_puct * p_j * sq / (double)(1 + (m - 1)) < U* then m -= 1, else stop;
+ *                 after the walk, if m < n_j and m <= 1 then m = 0.
+ *               The pruned count is n'_j = m; n'_b = n_b.
+ *   3 after it  everything uses n': the visited-children count of the example (and its overflow test against max_children) is the number
+ *               of edges with n' > 0, the stored (action | n' << 16) words and N = sum n' use n', for M < temp_moves the draw is the run's
+ *               draw over n' with N' = sum n' (so the played action is among the stored children); the first-maximum pick is unchanged,
+ *               since only other edges shrink.  A root with no visited edge behaves as without the setting.
+ *
+ * tafl_gselfplay_set_forced_playouts stores the setting on the batch (cfg == NULL: off).  tafl_gselfplay_begin and
+ *   tafl_gselfplay_begin_episodes latch it: a change during a run takes effect at the next begin.  k not finite, k <= 0 or k > 64:
+ *   TAFL_ERR_INVALID_ARG; non-zero flags or _reserved: TAFL_ERR_UNSUPPORTED (in both cases the setting is left as it was).  While it is
+ *   set tafl_gmatch_begin fails with TAFL_ERR_UNSUPPORTED.  The lock-step tafl_gmcts_* searches (their getters included) and the
+ *   rollout-mode tafl_selfplay_record ignore the setting.
+ * tafl_gselfplay_forced_playouts_stats: forced_sims = simulations whose root selection was forced, pruned_visits = sum (n - n'),
+ *   pruned_children = edges with n > 0 and n' == 0, full_moves = full moves made; counted on the device; valid from the begin until the
+ *   next tafl_gselfplay_begin / _begin_episodes on the batch (also after tafl_gselfplay_end), TAFL_ERR_INVALID_ARG when that run latched
+ *   no setting.
+ * Not offered: forcing or pruning in lock-step searches, matches or rollout-mode self-play, the raw counts beside the pruned ones, a k
+ *   that depends on the move, subtree reuse, temperatures other than 0 and 1. */
+typedef struct tafl_forced_playouts {
+    double k;                  /* 0 < k <= 64 (KataGo uses 2) */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[5];     /* 0 */
+} tafl_forced_playouts;        /* 32 bytes */
+typedef struct tafl_forced_playouts_stats { uint64_t forced_sims, pruned_visits, pruned_children, full_moves; } tafl_forced_playouts_stats;   /* 32 bytes */
+int tafl_gselfplay_set_forced_playouts(tafl_batch* b, const tafl_forced_playouts* cfg);
+int tafl_gselfplay_forced_playouts_stats(tafl_batch* b, tafl_forced_playouts_stats* out);
+
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
  * with the comma-separated vector, one line value1, one line value2; every line ends in '\n'.
