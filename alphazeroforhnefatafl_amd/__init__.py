@@ -6,13 +6,13 @@ thousands of concurrent games) as hand-written HIP kernels behind a C-ABI (inclu
 from . import abi
 from .abi import Ruleset, boards, rules
 
-__all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples",
+__all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples", "Pool",
            "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult", "playout_cap_is_full"]
 
 
 def __getattr__(name):
     # engine/mcts load libtaflhip.so (fails loudly if it is missing); abi is importable without it
-    if name in ("BatchedGameLogic", "GameBatch", "Examples"):
+    if name in ("BatchedGameLogic", "GameBatch", "Examples", "Pool"):
         from . import engine
         return getattr(engine, name)
     if name in ("MCTS", "MCTSArgs", "GuidedMCTS", "playout_cap_is_full"):

@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +94,15 @@ SYMBOLS = [
     ("tafl_gselfplay_playout_cap_stats", _i32, [_vp, _P(TaflPlayoutCapStats)]),
     ("tafl_gselfplay_set_forced_playouts", _i32, [_vp, _P(TaflForcedPlayouts)]),
     ("tafl_gselfplay_forced_playouts_stats", _i32, [_vp, _P(TaflForcedPlayoutsStats)]),
+    ("tafl_pool_create", _i32, [_vp, _u32, _u32, _P(_vp)]),
+    ("tafl_pool_destroy", _i32, [_vp]),
+    ("tafl_pool_clear", _i32, [_vp]),
+    ("tafl_pool_get_stats", _i32, [_vp, _P(TaflPoolStats)]),
+    ("tafl_pool_ingest", _i32, [_vp, _vp, _P(TaflPoolIngestResult)]),
+    ("tafl_pool_trim", _i32, [_vp, _u32]),
+    ("tafl_pool_sample", _i32, [_vp, _u64, _u64, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _i32]),
+    ("tafl_pool_gather", _i32, [_vp, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _i32]),
+    ("tafl_pool_read", _i32, [_vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     ("tafl_root_noise_eval", _i32, [_vp, _P(TaflRootNoise), _vp, _i32]),
     ("tafl_gmcts_root_priors", _i32, [_vp, _vp, _i32]),
     ("tafl_replay_append", _i32, [C.c_char_p, _P(_u8), _u8, _P(_u8), _u32, _u8, _u8, _u64]),

@@ -215,12 +215,26 @@ class TaflExamplesStats(C.Structure):
     _fields_ = [("dropped", C.c_uint64), ("overflowed", C.c_uint64), ("bad_index", C.c_uint64), ("device_bytes", C.c_uint64)]
 
 
+class TaflPoolStats(C.Structure):
+    """tafl_pool_stats: the counters of a training pool (tafl_pool_get_stats)."""
+    _fields_ = [("written", C.c_uint64), ("live", C.c_uint64), ("ingests", C.c_uint64), ("oldest_generation", C.c_uint64),
+                ("skipped_open", C.c_uint64), ("skipped_overflow", C.c_uint64), ("bad_slot", C.c_uint64), ("device_bytes", C.c_uint64)]
+
+
+class TaflPoolIngestResult(C.Structure):
+    """tafl_pool_ingest_result: what one tafl_pool_ingest took and skipped."""
+    _fields_ = [("taken", C.c_uint64), ("skipped_open", C.c_uint64), ("skipped_overflow", C.c_uint64), ("_reserved", C.c_uint64)]
+
+
+POOL_SAMPLE_SYM = 0x1            # tafl_pool_sample flags: draw one of the eight symmetries per row
+
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
                   "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
                   "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64, "tafl_match_opts": 32, "tafl_match_io": 72,
                   "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
-                  "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32}
+                  "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32,
+                  "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -229,7 +243,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_root_noise", TaflRootNoise), ("tafl_episode_opts", TaflEpisodeOpts),
                     ("tafl_episode_stats", TaflEpisodeStats), ("tafl_match_opts", TaflMatchOpts), ("tafl_match_io", TaflMatchIo),
                     ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats),
-                    ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats)]:
+                    ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats),
+                    ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

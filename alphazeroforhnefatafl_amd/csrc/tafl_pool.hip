@@ -1,0 +1,339 @@
+// tafl_pool.hip — the training pool on the device: k_pool_*, tafl_pool_*.
+#include "tafl_internal.hpp"
+#include "tafl_pool.hpp"
+
+#define POOL_TILE 256            /* examples per workgroup of the ingest kernels: one thread each, in the order of the per-example arrays */
+#define POOL_CHUNK 32            /* words of a row that pass through LDS at a time */
+#define POOL_LDS_STRIDE 33       /* words between two examples in LDS: odd, so that 32 lanes storing one word each of 32 examples hit 32 banks,
+                                    and 32 lanes reading the 8 quads of 4 examples do too (bank = (example + word) mod 32) */
+
+// The flags of the tile's examples and where a taken one stands among the tile's taken ones: ballot and popcount in the wave, the four
+// wave totals through LDS.  Returns the example's class (pool_take); lr = its rank in the tile, nt = the tile's taken examples.
+__device__ __forceinline__ uint32_t pool_tile_flags(const ExamplesMem& X, uint32_t E, uint32_t* wave_tot, uint32_t& info, uint32_t& e, uint32_t& lr, uint32_t& nt) {
+    const unsigned long long e64 = (unsigned long long)blockIdx.x * POOL_TILE + threadIdx.x;
+    e = (uint32_t)e64;
+    const uint32_t cls = e64 < E ? pool_take(X, e, info) : (uint32_t)POOL_NONE;
+    const unsigned long long m = __ballot(cls == POOL_TAKEN);
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    if (lane == 0) wave_tot[wave] = (uint32_t)__popcll(m);
+    __syncthreads();
+    lr = (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
+    nt = 0;
+    for (uint32_t w = 0; w < POOL_TILE / 64; ++w) { const uint32_t c = wave_tot[w]; if (w < wave) lr += c; nt += c; }
+    return cls;
+}
+
+// Ingest, pass 1: per tile the number of examples taken, skipped as open and skipped for overflow
+__global__ __launch_bounds__(POOL_TILE) void k_pool_count(ExamplesMem X, uint32_t E, uint32_t* blk_taken, uint32_t* blk_open, uint32_t* blk_over) {
+    __shared__ uint32_t wave_tot[POOL_TILE / 64], skipped[2];
+    if (threadIdx.x < 2) skipped[threadIdx.x] = 0;
+    uint32_t info, e, lr, nt;
+    const uint32_t cls = pool_tile_flags(X, E, wave_tot, info, e, lr, nt);        // (its barrier also publishes the zeroes)
+    const unsigned long long mo = __ballot(cls == POOL_OPEN), mv = __ballot(cls == POOL_OVERFLOW);
+    if ((threadIdx.x & 63u) == 0) { atomicAdd(&skipped[0], (uint32_t)__popcll(mo)); atomicAdd(&skipped[1], (uint32_t)__popcll(mv)); }
+    __syncthreads();
+    if (threadIdx.x == 0) { blk_taken[blockIdx.x] = nt; blk_open[blockIdx.x] = skipped[0]; blk_over[blockIdx.x] = skipped[1]; }
+}
+
+// Ingest, pass 2: the exclusive prefix of the tiles' taken counts, by one workgroup that walks them POOL_TILE at a time with a carry (no
+// width limit), and the three totals res = { T, skipped open, skipped overflow }
+__global__ __launch_bounds__(POOL_TILE) void k_pool_scan(const uint32_t* blk_taken, const uint32_t* blk_open, const uint32_t* blk_over, uint32_t nb, uint32_t* prefix,
+                                                         unsigned long long* res) {
+    __shared__ uint32_t wave_tot[POOL_TILE / 64];
+    __shared__ unsigned long long sums[2];
+    if (threadIdx.x < 2) sums[threadIdx.x] = 0;
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    unsigned long long open = 0, over = 0;
+    for (uint32_t c0 = 0; c0 < nb; c0 += POOL_TILE) {
+        const uint32_t i = c0 + threadIdx.x;
+        const uint32_t v = i < nb ? blk_taken[i] : 0u;
+        if (i < nb) { open += blk_open[i]; over += blk_over[i]; }
+        uint32_t incl = v;
+        for (uint32_t d = 1; d < 64; d <<= 1) { const uint32_t u = __shfl_up(incl, d, 64); if (lane >= d) incl += u; }
+        if (lane == 63) wave_tot[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+        for (uint32_t w = 0; w < POOL_TILE / 64; ++w) { const uint32_t c = wave_tot[w]; if (w < wave) before += c; total += c; }
+        if (i < nb) prefix[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    atomicAdd(&sums[0], open); atomicAdd(&sums[1], over);
+    __syncthreads();
+    if (threadIdx.x == 0) { res[0] = carry; res[1] = sums[0]; res[2] = sums[1]; }
+}
+
+// Ingest, pass 3: the rows.  The examples' arrays are column-major (word w of example (j, g) at [(j * BW + w) * G + g]), so a wave reads
+// one word of 64 consecutive examples per load; a row is contiguous, and the tile's taken examples have consecutive ranks, hence
+// consecutive slots: the tile's rows are one contiguous piece of the pool (two where the ring wraps).  POOL_CHUNK words of every taken
+// example go through LDS - example-major there - and leave as 16-byte stores, eight consecutive lanes per 128-byte piece of a row.
+__global__ __launch_bounds__(POOL_TILE) void k_pool_copy(ExamplesMem X, uint32_t E, PoolMem P, const uint32_t* prefix, const unsigned long long* res,
+                                                         unsigned long long written, uint32_t generation) {
+    __shared__ uint32_t wave_tot[POOL_TILE / 64];
+    __shared__ uint32_t tile[POOL_TILE * POOL_LDS_STRIDE];
+    uint32_t info, e, lr, nt;
+    const bool taken = pool_tile_flags(X, E, wave_tot, info, e, lr, nt) == POOL_TAKEN;
+    if (nt == 0) return;                                                        // (block-uniform)
+    const uint32_t T = (uint32_t)res[0], base = prefix[blockIdx.x], g = e % X.G, j = e / X.G;
+    const uint32_t slot0 = (uint32_t)((written + base) % P.C);
+    uint4* rows = reinterpret_cast<uint4*>(P.rows);
+    for (uint32_t w0 = 0; w0 < P.RW; w0 += POOL_CHUNK) {
+        const uint32_t cw = P.RW - w0 < POOL_CHUNK ? P.RW - w0 : POOL_CHUNK, qpr = cw / 4u;       // (RW is a multiple of 4)
+        if (taken)
+            for (uint32_t u0 = 0; u0 < cw; u0 += 4) {
+                uint32_t v[4];
+                TAFL_UNROLL for (uint32_t u = 0; u < 4; ++u) v[u] = pool_row_word(X, j, g, info, w0 + u0 + u, generation);
+                TAFL_UNROLL for (uint32_t u = 0; u < 4; ++u) tile[lr * POOL_LDS_STRIDE + u0 + u] = v[u];
+            }
+        __syncthreads();
+        for (uint32_t q = threadIdx.x; q < nt * qpr; q += POOL_TILE) {
+            const uint32_t row = q / qpr, wq = q % qpr;
+            uint32_t slot;
+            if (!pool_place(written, base + row, T, P.C, slot)) continue;
+            unsigned long long s = (unsigned long long)slot0 + row;            // (the same slot, without a 64-bit division per quad)
+            if (s >= P.C) s %= P.C;
+            const uint32_t* src = tile + row * POOL_LDS_STRIDE + 4u * wq;
+            rows[((size_t)s * P.RW + w0) / 4u + wq] = make_uint4(src[0], src[1], src[2], src[3]);
+        }
+        __syncthreads();
+    }
+}
+
+// Minibatch rows (tafl_pool_sample: DRAW, tafl_pool_gather: slot_in / sym_in): row i = the row of a slot under a symmetry, in the shape
+// of k_examples_gather - the dense policy row is built in LDS, which is all zero between two rows, and streamed out with full-width
+// stores - reading one contiguous row.  One workgroup serves rows blockIdx.x, blockIdx.x + gridDim.x, ...
+template <bool DRAW, bool VEC>
+__global__ __launch_bounds__(256) void k_pool_rows(PoolMem P, unsigned long long written, unsigned long long live, unsigned long long seed, unsigned long long step,
+                                                   uint32_t row_base, uint32_t flags, const uint32_t* slot_in, const uint8_t* sym_in, uint32_t count, uint32_t n, uint32_t A,
+                                                   uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym) {
+    extern __shared__ __align__(16) float lds_row[];                          // [A]
+    for (uint32_t v = threadIdx.x; v < A; v += 256) lds_row[v] = 0.0f;
+    __syncthreads();
+    const uint32_t nn = n * n;
+    for (uint32_t i = blockIdx.x; i < count; i += gridDim.x) {
+        uint32_t slot, s;                                                       // (block-uniform)
+        if constexpr (DRAW) pool_draw(seed, step, row_base + i, written, live, P.C, flags, slot, s);
+        else { slot = slot_in[i]; s = sym_in ? (sym_in[i] & 7u) : 0u; }
+        const bool ok = DRAW || pool_slot_live(slot, written, live, P.C);
+        const uint32_t* row = P.rows + (size_t)(ok ? slot : 0u) * P.RW;
+        const uint32_t nc = ok ? pool_row_children(row, P.BW) : 0u;
+        if (pi) for (uint32_t k = threadIdx.x; k < nc; k += 256) { uint32_t a; const float p = pool_out_pi(row, P.BW, k, n, s, a); lds_row[a] = p; }
+        if (boards && threadIdx.x < nn) {
+            uint32_t dst; const uint8_t v = pool_out_tile(row, threadIdx.x, n, s, dst);
+            boards[(size_t)i * nn + dst] = ok ? v : (uint8_t)0;
+        }
+        if (threadIdx.x == 0) {
+            if (!ok) atomicAdd(&P.counters[POOL_BAD_SLOT], 1ull);
+            if (sides) sides[i] = ok ? pool_row_side(row, P.BW) : (uint8_t)0;
+            if (z) z[i] = ok ? pool_row_z(row, P.BW) : 0.0f;
+            if (out_slot) out_slot[i] = slot;
+            if (out_sym) out_sym[i] = (uint8_t)s;
+        }
+        if (pi) {
+            __syncthreads();
+            if constexpr (VEC) {
+                float4* dst = reinterpret_cast<float4*>(pi + (size_t)i * A); float4* src = reinterpret_cast<float4*>(lds_row);
+                for (uint32_t v = threadIdx.x; v < A / 4u; v += 256) { dst[v] = src[v]; src[v] = make_float4(0.f, 0.f, 0.f, 0.f); }
+            } else {
+                float* dst = pi + (size_t)i * A;
+                for (uint32_t v = threadIdx.x; v < A; v += 256) { dst[v] = lds_row[v]; lds_row[v] = 0.0f; }
+            }
+            __syncthreads();
+        }
+    }
+}
+
+struct tafl_pool {
+    tafl_ctx* ctx;
+    PoolMem mem;
+    PoolBook book;                       // written, live, ingests and the rows per generation
+    uint64_t skipped_open = 0, skipped_overflow = 0;
+    DevBuf rows, counters, blk, res;
+    DevBuf g_slot, g_sym, g_boards, g_sides, g_pi, g_z;      // staging of calls with host pointers
+    size_t device_bytes = 0;
+    int need(DevBuf& d, size_t bytes) { device_bytes -= d.cap; const int rc = d.ensure(bytes); device_bytes += d.cap; return rc; }
+};
+
+#define POOLCHK(p, name) do { if (!(p)) return fail(TAFL_ERR_INVALID_ARG, name ": null pool"); HIPCHK(hipSetDevice((p)->ctx->device)); } while (0)
+#define POOLNEED(buf, bytes) do { if (p->need(buf, bytes)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed"); } while (0)
+
+// one launch of k_pool_rows on the context's stream; every pointer is a device pointer
+static int pool_rows_launch(tafl_pool* p, bool draw, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t flags, const uint32_t* slot, const uint8_t* sym, uint32_t count,
+                            uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym) {
+    tafl_ctx* c = p->ctx;
+    const uint32_t A = c->n * c->n * 2u * (c->n - 1u);
+    const uint32_t grid = count < 8192u ? count : 8192u;
+    const bool vec = ((uintptr_t)pi & 15u) == 0;
+    auto go = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), A * sizeof(float), c->stream, p->mem, (unsigned long long)p->book.written, (unsigned long long)p->book.live,
+                           (unsigned long long)seed, (unsigned long long)step, row_base, flags, slot, sym, count, c->n, A, boards, sides, pi, z, out_slot, out_sym);
+    };
+    if (draw) { if (vec) go(k_pool_rows<true, true>); else go(k_pool_rows<true, false>); }
+    else { if (vec) go(k_pool_rows<false, true>); else go(k_pool_rows<false, false>); }
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
+// tafl_pool_sample (draw) and tafl_pool_gather: with host pointers the rows are written into device staging and copied out, a chunk at a time
+static int pool_rows(tafl_pool* p, bool draw, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t flags, const uint32_t* slot, const uint8_t* sym, uint32_t count,
+                     uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym, int ptrs_are_device) {
+    if (ptrs_are_device) return pool_rows_launch(p, draw, seed, step, row_base, flags, slot, sym, count, boards, sides, pi, z, out_slot, out_sym);
+    tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
+    const size_t A = (size_t)c->n * c->n * 2u * (c->n - 1u), nn = (size_t)c->n * c->n;
+    const uint32_t chunk = count < 8192u ? count : 8192u;
+    POOLNEED(p->g_slot, 4 * (size_t)chunk); POOLNEED(p->g_sym, chunk); POOLNEED(p->g_sides, chunk); POOLNEED(p->g_z, 4 * (size_t)chunk);
+    if (boards) POOLNEED(p->g_boards, nn * chunk);
+    if (pi) POOLNEED(p->g_pi, 4 * A * chunk);
+    for (uint32_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint32_t k = count - i0 < chunk ? count - i0 : chunk;
+        if (!draw) {
+            HIPCHK(hipMemcpyAsync(p->g_slot.p, slot + i0, 4 * (size_t)k, hipMemcpyHostToDevice, s));
+            if (sym) HIPCHK(hipMemcpyAsync(p->g_sym.p, sym + i0, k, hipMemcpyHostToDevice, s));
+        }
+        const int rc = pool_rows_launch(p, draw, seed, step, row_base + i0, flags, p->g_slot.as<const uint32_t>(), (!draw && sym) ? p->g_sym.as<const uint8_t>() : nullptr, k,
+                                        boards ? p->g_boards.as<uint8_t>() : nullptr, sides ? p->g_sides.as<uint8_t>() : nullptr, pi ? p->g_pi.as<float>() : nullptr,
+                                        z ? p->g_z.as<float>() : nullptr, (draw && out_slot) ? p->g_slot.as<uint32_t>() : nullptr, (draw && out_sym) ? p->g_sym.as<uint8_t>() : nullptr);
+        if (rc) return rc;
+        if (boards) COPY_OUT(boards + (size_t)i0 * nn, p->g_boards.p, nn * k, s);
+        if (sides) COPY_OUT(sides + i0, p->g_sides.p, k, s);
+        if (pi) COPY_OUT(pi + (size_t)i0 * A, p->g_pi.p, A * k, s);
+        if (z) COPY_OUT(z + i0, p->g_z.p, k, s);
+        if (draw && out_slot) COPY_OUT(out_slot + i0, p->g_slot.p, k, s);
+        if (draw && out_sym) COPY_OUT(out_sym + i0, p->g_sym.p, k, s);
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return TAFL_OK;
+}
+
+extern "C" {
+
+int tafl_pool_create(tafl_ctx* c, uint32_t capacity, uint32_t max_children, tafl_pool** out) {
+    if (!c || !out || capacity == 0 || max_children == 0 || max_children > 0xFFFFu)
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_create: bad argument (capacity >= 1, max_children in 1..65535)");
+    HIPCHK(hipSetDevice(c->device));
+    tafl_pool* p = new (std::nothrow) tafl_pool();
+    if (!p) return fail(TAFL_ERR_OOM, "out of host memory");
+    c->live_batches += 1;                                    // (the context outlives its pools as it outlives its batches)
+    p->ctx = c;
+    PoolMem& M = p->mem;
+    M.C = capacity; M.Kp = max_children; M.BW = (c->n * c->n + 3u) / 4u; M.RW = pool_row_words(M.BW, M.Kp);
+    if (p->need(p->rows, 4 * (size_t)capacity * M.RW) || p->need(p->counters, 8 * POOL_COUNTERS) || p->need(p->res, 8 * 3)) {
+        tafl_pool_destroy(p);
+        return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_pool_create)");
+    }
+    p->rows.bind(M.rows); p->counters.bind(M.counters);
+    const int rc = tafl_pool_clear(p);
+    if (rc) { tafl_pool_destroy(p); return rc; }
+    *out = p;
+    return TAFL_OK;
+}
+int tafl_pool_destroy(tafl_pool* p) {
+    if (!p) return TAFL_OK;
+    (void)hipSetDevice(p->ctx->device);
+    (void)hipStreamSynchronize(p->ctx->stream);
+    p->ctx->live_batches -= 1;
+    delete p;
+    return TAFL_OK;
+}
+int tafl_pool_clear(tafl_pool* p) {
+    POOLCHK(p, "tafl_pool_clear");
+    HIPCHK(hipMemsetAsync(p->counters.p, 0, 8 * POOL_COUNTERS, p->ctx->stream));
+    p->book.clear(); p->skipped_open = p->skipped_overflow = 0;
+    return sync_ok(p->ctx);
+}
+int tafl_pool_get_stats(tafl_pool* p, tafl_pool_stats* out) {
+    POOLCHK(p, "tafl_pool_get_stats");
+    if (!out) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_get_stats: null argument");
+    unsigned long long h[POOL_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, p->counters.p, sizeof h, hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    memset(out, 0, sizeof *out);
+    out->written = p->book.written; out->live = p->book.live; out->ingests = p->book.ingests; out->oldest_generation = p->book.oldest_generation();
+    out->skipped_open = p->skipped_open; out->skipped_overflow = p->skipped_overflow; out->bad_slot = h[POOL_BAD_SLOT];
+    out->device_bytes = p->device_bytes;
+    return TAFL_OK;
+}
+
+int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* out) {
+    POOLCHK(p, "tafl_pool_ingest");
+    if (!ex) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: null examples object");
+    if (ex->ctx != p->ctx) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the examples object belongs to another context (board size or device)");
+    if (ex->max_children > p->mem.Kp) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the examples hold more policy entries (max_children) than a row of the pool");
+    if (p->book.ingests >= 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the generation exceeds 32 bits");
+    tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
+    const uint32_t E = ex->n_games * ex->max_moves, nb = (uint32_t)(((unsigned long long)E + POOL_TILE - 1) / POOL_TILE);       // (E fits 32 bits: tafl_examples_create)
+    POOLNEED(p->blk, 16 * (size_t)nb);
+    uint32_t* taken = p->blk.as<uint32_t>(); uint32_t* open = taken + nb; uint32_t* over = open + nb; uint32_t* prefix = over + nb;
+    unsigned long long* res = p->res.as<unsigned long long>();
+    const uint32_t generation = (uint32_t)(p->book.ingests + 1);
+    hipLaunchKernelGGL(k_pool_count, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, E, taken, open, over);
+    hipLaunchKernelGGL(k_pool_scan, dim3(1), dim3(POOL_TILE), 0, s, (const uint32_t*)taken, (const uint32_t*)open, (const uint32_t*)over, nb, prefix, res);
+    hipLaunchKernelGGL(k_pool_copy, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, E, p->mem, (const uint32_t*)prefix, (const unsigned long long*)res,
+                       (unsigned long long)p->book.written, generation);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[3];
+    HIPCHK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    p->book.took(h[0], p->mem.C); p->skipped_open += h[1]; p->skipped_overflow += h[2];
+    if (out) { out->taken = h[0]; out->skipped_open = h[1]; out->skipped_overflow = h[2]; out->_reserved = 0; }
+    return TAFL_OK;
+}
+
+int tafl_pool_trim(tafl_pool* p, uint32_t keep_generations) {
+    POOLCHK(p, "tafl_pool_trim");
+    if (keep_generations == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_trim: keep_generations must be at least 1");
+    p->book.trim(keep_generations);
+    return TAFL_OK;
+}
+
+int tafl_pool_sample(tafl_pool* p, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t count, uint32_t flags, uint8_t* boards, uint8_t* sides, float* pi, float* z,
+                     uint32_t* out_slot, uint8_t* out_sym, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_sample");
+    if (flags & ~(uint32_t)TAFL_POOL_SAMPLE_SYM) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_sample: unknown flag bits");
+    if ((unsigned long long)row_base + count > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample: row_base + count exceeds 32 bits");
+    if (p->book.live == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample: the pool holds no live row");
+    if (count == 0) return TAFL_OK;
+    return pool_rows(p, true, seed, step, row_base, flags, nullptr, nullptr, count, boards, sides, pi, z, out_slot, out_sym, ptrs_are_device);
+}
+
+int tafl_pool_gather(tafl_pool* p, const uint32_t* slot, const uint8_t* sym, uint32_t count, uint8_t* boards, uint8_t* sides, float* pi, float* z, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_gather");
+    if (!slot && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather: null slot");
+    if (count == 0) return TAFL_OK;
+    if (!ptrs_are_device)
+        for (uint32_t i = 0; i < count; ++i) {
+            if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather: slot " + std::to_string(slot[i]) + " (row " + std::to_string(i) + ") is not live");
+            if (sym && sym[i] > 7) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather: sym must be in 0..7");
+        }
+    return pool_rows(p, false, 0, 0, 0, 0, slot, sym, count, boards, sides, pi, z, nullptr, nullptr, ptrs_are_device);
+}
+
+// the sparse form of rows, for hosts that store or inspect them: one copy of the span of rows between the lowest and the highest slot asked for
+int tafl_pool_read(tafl_pool* p, const uint32_t* slot, uint32_t count, uint32_t* n_children, uint32_t* move_no, uint32_t* generation, uint32_t* actions, uint32_t* visits) {
+    POOLCHK(p, "tafl_pool_read");
+    if (!slot && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_read: null slot");
+    if (count == 0) return TAFL_OK;
+    uint32_t lo = 0xFFFFFFFFu, hi = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_read: slot " + std::to_string(slot[i]) + " (row " + std::to_string(i) + ") is not live");
+        lo = std::min(lo, slot[i]); hi = std::max(hi, slot[i]);
+    }
+    const size_t RW = p->mem.RW, Kp = p->mem.Kp, BW = p->mem.BW;
+    std::vector<uint32_t> h(((size_t)hi - lo + 1) * RW);
+    HIPCHK(hipMemcpyAsync(h.data(), p->mem.rows + (size_t)lo * RW, 4 * h.size(), hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    for (uint32_t i = 0; i < count; ++i) {
+        const uint32_t* row = h.data() + ((size_t)slot[i] - lo) * RW;
+        if (n_children) n_children[i] = pool_row_children(row, (uint32_t)BW);
+        if (move_no) move_no[i] = row[BW + PR_MOVE_NO];
+        if (generation) generation[i] = row[BW + PR_GENERATION];
+        for (size_t k = 0; k < Kp; ++k) {
+            const uint32_t w = row[BW + PR_HEAD + k];
+            if (actions) actions[(size_t)i * Kp + k] = w & 0xFFFFu;
+            if (visits) visits[(size_t)i * Kp + k] = w >> 16;
+        }
+    }
+    return TAFL_OK;
+}
+
+}  // extern "C"

@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -77,6 +77,11 @@ class BatchedGameLogic:
         """A device-resident buffer of training examples for batches of `n_games` games: room for `max_moves` examples per game with up
         to `max_children` policy entries each (max_children >= n_sims can never overflow).  Filled by GameBatch.selfplay_record."""
         return Examples(self, n_games, max_moves, max_children)
+
+    def new_pool(self, capacity: int, max_children: int) -> "Pool":
+        """A training pool on the device: a ring of `capacity` finished examples with up to `max_children` policy entries each, filled by
+        Pool.ingest from Examples objects and sampled by Pool.sample (tafl_pool_*)."""
+        return Pool(self, capacity, max_children)
 
     def state_from_fen(self, fen: str, side_to_play: int | None = None) -> TaflState:
         st = TaflState()
@@ -655,3 +660,124 @@ class Examples:
                                          boards.ctypes.data_as(C.c_void_p), sides.ctypes.data_as(C.c_void_p), pi.ctypes.data_as(C.c_void_p),
                                          z.ctypes.data_as(C.c_void_p), fin.ctypes.data_as(C.c_void_p), 0))
         return boards, sides, pi, z, fin
+
+
+class Pool:
+    """A fixed-capacity window over finished training examples in HBM (tafl_pool).  The q-th row ever taken lives in slot q % capacity;
+    the live rows are the newest min(written, capacity), minus what trim removed.  It outlives the Examples objects it was filled from."""
+
+    def __init__(self, logic: BatchedGameLogic, capacity: int, max_children: int):
+        self.logic = logic
+        self.capacity, self.max_children = capacity, max_children
+        self._h = C.c_void_p()
+        check(lib().tafl_pool_create(logic._h, capacity, max_children, C.byref(self._h)))
+        logic._batches.add(self)          # closed with the context, like its batches
+
+    def close(self):
+        if self._h:
+            lib().tafl_pool_destroy(self._h)
+            self._h = C.c_void_p()
+            self.logic._batches.discard(self)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def ingest(self, examples: Examples):
+        """Takes every finished example of `examples` (final = 1, with a policy) in ascending index order as one generation; the object
+        is not modified (clear it afterwards).  Returns (taken, skipped_open, skipped_overflow) of this call."""
+        out = TaflPoolIngestResult()
+        check(lib().tafl_pool_ingest(self._h, examples._h, C.byref(out)))
+        return out.taken, out.skipped_open, out.skipped_overflow
+
+    def trim(self, keep_generations: int):
+        """Only the rows of the newest `keep_generations` ingests stay live (numItersForTrainExamplesHistory)."""
+        check(lib().tafl_pool_trim(self._h, keep_generations))
+
+    def clear(self):
+        """Empties the pool and zeroes its counters."""
+        check(lib().tafl_pool_clear(self._h))
+
+    def stats(self) -> TaflPoolStats:
+        """written, live, ingests, oldest_generation, skipped_open, skipped_overflow, bad_slot, device_bytes."""
+        st = TaflPoolStats()
+        check(lib().tafl_pool_get_stats(self._h, C.byref(st)))
+        return st
+
+    def _outputs(self, k, device, dev=None):
+        n, A = self.logic.side_len, self.logic.action_size
+        if device:
+            import torch
+            return (torch.empty((k, n, n), dtype=torch.uint8, device=dev), torch.empty((k,), dtype=torch.uint8, device=dev),
+                    torch.empty((k, A), dtype=torch.float32, device=dev), torch.empty((k,), dtype=torch.float32, device=dev))
+        import numpy as np
+        return np.zeros((k, n, n), np.uint8), np.zeros((k,), np.uint8), np.zeros((k, A), np.float32), np.zeros((k,), np.float32)
+
+    def sample(self, count: int, seed: int, step: int, row_base: int = 0, symmetries: bool = True, device: bool = False):
+        """`count` uniformly drawn live rows (with replacement) as (boards uint8 [count, n, n], sides uint8, pi float32 [count, action_size],
+        z float32, slot, sym): row i is drawn from (seed, step, row_base + i) alone, so rank k of a data-parallel trainer passes
+        row_base = k * count.  symmetries: one of the eight board symmetries per row, else the identity.  device=True: torch tensors on
+        the context's device come back (slot int32, sym uint8) and nothing crosses PCIe; otherwise numpy arrays (slot uint32)."""
+        flags = abi.POOL_SAMPLE_SYM if symmetries else 0
+        vp = C.c_void_p
+        if device:
+            import torch
+            dev = torch.device("cuda", self.logic.device)
+            out = self._outputs(count, True, dev)
+            slot, sym = torch.empty((count,), dtype=torch.int32, device=dev), torch.empty((count,), dtype=torch.uint8, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_sample(self._h, seed, step, row_base, count, flags, *[vp(t.data_ptr()) for t in out], vp(slot.data_ptr()), vp(sym.data_ptr()), 1))
+            self.logic.sync()
+            return (*out, slot, sym)
+        import numpy as np
+        out = self._outputs(count, False)
+        slot, sym = np.zeros((count,), np.uint32), np.zeros((count,), np.uint8)
+        check(lib().tafl_pool_sample(self._h, seed, step, row_base, count, flags, *[a.ctypes.data_as(vp) for a in out], slot.ctypes.data_as(vp), sym.ctypes.data_as(vp), 0))
+        return (*out, slot, sym)
+
+    def gather(self, slots, sym=None, device: bool = False):
+        """(boards, sides, pi, z) of the rows in `slots` under the board symmetries `sym` (0..7 each, None: identity): the bytes
+        Examples.gather gave for the source examples.  device=False: sequences or numpy arrays in, numpy arrays out; a slot that is not
+        live raises.  device=True: torch tensors (int32 / uint8) on the context's device in and out; a slot that is not live gives an
+        all-zero row and counts in stats().bad_slot."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            sl = slots.contiguous()
+            if sl.dtype != torch.int32 or not sl.is_cuda or sl.device.index != self.logic.device:
+                raise ValueError("gather(device=True): slots must be an int32 tensor on the context's device")
+            k = int(sl.numel())
+            sy = None
+            if sym is not None:
+                sy = sym.contiguous()
+                if sy.dtype != torch.uint8 or sy.device != sl.device or sy.numel() != k:
+                    raise ValueError("gather(device=True): sym must be a uint8 tensor on the same device, one per slot")
+            out = self._outputs(k, True, sl.device)
+            torch.cuda.current_stream(sl.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_gather(self._h, vp(sl.data_ptr()), vp(sy.data_ptr()) if sy is not None else None, k, *[vp(t.data_ptr()) for t in out], 1))
+            self.logic.sync()
+            return out
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        k = int(sl.size)
+        sy = None if sym is None else np.ascontiguousarray(sym, dtype=np.uint8)
+        if sy is not None and sy.size != k:
+            raise ValueError("gather: one sym per slot")
+        out = self._outputs(k, False)
+        check(lib().tafl_pool_gather(self._h, sl.ctypes.data_as(vp), sy.ctypes.data_as(vp) if sy is not None else None, k, *[a.ctypes.data_as(vp) for a in out], 0))
+        return out
+
+    def read(self, slots):
+        """The sparse form of the rows in `slots` as numpy arrays: (n_children [k], move_no [k], generation [k], actions [k, max_children],
+        visits [k, max_children]) (tafl_pool_read; not a hot path)."""
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        k, K = int(sl.size), self.max_children
+        nc, mv, gen = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.uint32)
+        acts, vis = np.zeros((k, K), np.uint32), np.zeros((k, K), np.uint32)
+        vp = C.c_void_p
+        check(lib().tafl_pool_read(self._h, sl.ctypes.data_as(vp), k, nc.ctypes.data_as(vp), mv.ctypes.data_as(vp), gen.ctypes.data_as(vp),
+                                   acts.ctypes.data_as(vp), vis.ctypes.data_as(vp)))
+        return nc, mv, gen, acts, vis

@@ -819,6 +819,89 @@ typedef struct tafl_forced_playouts_stats { uint64_t forced_sims, pruned_visits,
 int tafl_gselfplay_set_forced_playouts(tafl_batch* b, const tafl_forced_playouts* cfg);
 int tafl_gselfplay_forced_playouts_stats(tafl_batch* b, tafl_forced_playouts_stats* out);
 
+/* ---- training pool: a window over finished examples, sampled on the device ------------------------------------------
+ * The piece between "self-play wrote examples" and "the trainer takes a minibatch": a fixed-capacity ring of finished examples in HBM that
+ * outlives the tafl_examples objects it was filled from (alpha-zero-general keeps the examples of the last N iterations and trains on
+ * shuffled batches of them).  tafl_pool_ingest compacts the finished examples of an examples object into it, tafl_pool_sample draws rows
+ * uniformly under random board symmetries.  Build-defined.  Nothing else in this header behaves differently.
+ *
+ * Rows and slots.  A pool has `capacity` C rows (1 <= C < 2^32) of `max_children` Kp (1..65535) policy entries.  The q-th row ever taken
+ *   (q from 0) lives in slot q mod C.  live = min(written, C) minus what tafl_pool_trim removed; the live rows are those with q in
+ *   [written - live, written); a slot is live if and only if it holds one of them.  A row is contiguous: the ceil(side_len^2 / 4) board
+ *   words of the example, n_children | side << 16, N, move_no, generation, z, Kp policy words action | Nsa << 16 in canonical order (zero
+ *   beyond n_children), padded to a multiple of 16 bytes.  tafl_pool_create allocates
+ *     capacity * 16 * ceil((ceil(side_len^2 / 4) + 5 + max_children) / 4) + 32 bytes
+ *   on the context's device; the first ingest adds 16 bytes per 256 examples of room of the largest examples object ingested
+ *   (n_games * max_moves), calls with host pointers add their staging; tafl_pool_stats.device_bytes counts all of it.  Destroy a pool
+ *   before its context.
+ * tafl_pool_ingest, as a serial loop over the per-example arrays of `ex` (G = n_games):
+ *     T = 0
+ *     for e = 0 .. G * max_moves - 1, ascending (j = e / G, g = e % G):
+ *         if j >= min(len[g], max_moves): continue                       no example there
+ *         if the example has the overflow mark: skipped_overflow += 1; continue
+ *         if final == 0:                        skipped_open += 1;     continue
+ *         rank[e] = T; T += 1
+ *     generation = ingests + 1
+ *     the example of rank r is written iff r >= T - min(T, C); its row number is q = written + r, its slot q mod C
+ *     written += T; ingests += 1
+ *   Examples with r < T - C are not stored at all, so no two stores of an ingest name the same slot.  The ranks come from a scan, not from
+ *   atomics: the slot of every example is the one above on every run.  `ex` is not modified; ingesting it twice takes its examples twice
+ *   (the documented use is tafl_examples_finalize or an episodes run, then tafl_pool_ingest, then tafl_examples_clear).  An ingest with
+ *   T = 0 still counts as a generation.  `ex` of another context (hence another board size or device), or ex->max_children > Kp:
+ *   TAFL_ERR_INVALID_ARG.  out (may be NULL) receives T and the two skip counts of this call.  The call is synchronous.
+ *   Ordering: the ingest is enqueued on the context's stream.  That orders it after tafl_examples_finalize, after tafl_selfplay_record
+ *   (which returns with its streams joined) and after every step of a guided run (tafl_gselfplay_*, tafl_gmatch_*) of a batch of the
+ *   SAME context, open or ended.  A guided run of a batch of another context of the device writes `ex` on that context's stream: it
+ *   must have been ended (tafl_gselfplay_end synchronises) before the ingest.  An examples object keeps no reference to the batches
+ *   that record into it, so there is nothing an ingest could join.
+ * tafl_pool_trim keeps only the rows of the newest keep_generations ingests (numItersForTrainExamplesHistory): bookkeeping on the host that
+ *   lowers `live`; keep_generations == 0: TAFL_ERR_INVALID_ARG.  tafl_pool_clear empties the pool and zeroes all counters.
+ * tafl_pool_sample: row i < count of the outputs uses row = row_base + i (a sum above 32 bits: TAFL_ERR_INVALID_ARG) and
+ *     dk   = sim_key(game_key(seed, step) ^ 0x504F4F4C44524157, row)       the taflmix32 family of the playouts
+ *     a    = (ply_rand(dk, 0) * live) >> 32                                age rank, 0 = the oldest live row
+ *     slot = (written - live + a) mod C                                    64-bit arithmetic
+ *     sym  = flags & TAFL_POOL_SAMPLE_SYM ? ply_rand(dk, 1) >> 29 : 0
+ *   Integers only, a pure function of (seed, step, row, written, live, C): rank k of a data-parallel trainer passes row_base = k * count and
+ *   the ranks together draw exactly the rows of one big call.  Row i is what tafl_pool_gather writes for (slot, sym); out_slot[i] and
+ *   out_sym[i] (may be NULL) receive the draw.  live == 0: TAFL_ERR_INVALID_ARG; unknown flag bits: TAFL_ERR_UNSUPPORTED.
+ * tafl_pool_gather: row i = the row in slot[i] under symmetry sym[i] (NULL: identity), exactly the bytes tafl_examples_gather wrote for the
+ *   source example under that symmetry: boards[i * side_len^2 ..], sides[i], pi[i * tafl_action_size ..] with
+ *   pi[sigma(action)] = (float)((double)Nsa / (double)N), z[i].  Any output pointer may be NULL.
+ *   ptrs_are_device = 0 (both calls): host pointers; a slot that is not live or a sym above 7 fails the call with TAFL_ERR_INVALID_ARG
+ *   before anything is written.  ptrs_are_device = 1: every pointer is a device pointer of the context's device, the kernel is enqueued on
+ *   the context's stream (tafl_sync joins it) and nothing is read back; such a row is all zero and counted in tafl_pool_stats.bad_slot,
+ *   sym is taken modulo 8.
+ * tafl_pool_read: the sparse form of the rows in slot[0 .. count) (host pointers; a slot that is not live: TAFL_ERR_INVALID_ARG):
+ *   n_children[i], move_no[i], generation[i], actions / visits [i * Kp + k].  Any output may be NULL.  It copies every row between the
+ *   lowest and the highest slot asked for to the host: not a hot path.
+ * Not offered: saving and loading a pool, weighted or prioritised sampling, sampling without replacement, de-duplication of positions,
+ *   ingesting examples that are not final, a pool that spans devices. */
+typedef struct tafl_pool tafl_pool;                 /* opaque, owned by the ctx's device */
+typedef struct tafl_pool_stats {
+    uint64_t written;          /* rows ever taken by ingests (also those that fell out of the window) */
+    uint64_t live;             /* rows that can be sampled now */
+    uint64_t ingests;          /* tafl_pool_ingest calls that succeeded = the newest generation */
+    uint64_t oldest_generation;/* generation of the oldest live row (0: empty) */
+    uint64_t skipped_open;     /* over all ingests: recorded examples with final == 0 */
+    uint64_t skipped_overflow; /* over all ingests: recorded examples with the overflow mark (no policy) */
+    uint64_t bad_slot;         /* rows of device-pointer gathers whose slot was not live */
+    uint64_t device_bytes;
+} tafl_pool_stats;                                  /* 64 bytes */
+typedef struct tafl_pool_ingest_result { uint64_t taken, skipped_open, skipped_overflow, _reserved; } tafl_pool_ingest_result;   /* 32 bytes */
+#define TAFL_POOL_SAMPLE_SYM 0x1u   /* draw one of the eight symmetries per row; without it sym = 0 */
+int tafl_pool_create(tafl_ctx* ctx, uint32_t capacity, uint32_t max_children, tafl_pool** out);
+int tafl_pool_destroy(tafl_pool* pool);
+int tafl_pool_clear(tafl_pool* pool);
+int tafl_pool_get_stats(tafl_pool* pool, tafl_pool_stats* out);
+int tafl_pool_ingest(tafl_pool* pool, tafl_examples* ex, tafl_pool_ingest_result* out);
+int tafl_pool_trim(tafl_pool* pool, uint32_t keep_generations);
+int tafl_pool_sample(tafl_pool* pool, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t count, uint32_t flags,
+                     uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym, int ptrs_are_device);
+int tafl_pool_gather(tafl_pool* pool, const uint32_t* slot, const uint8_t* sym, uint32_t count,
+                     uint8_t* boards, uint8_t* sides, float* pi, float* z, int ptrs_are_device);
+int tafl_pool_read(tafl_pool* pool, const uint32_t* slot, uint32_t count, uint32_t* n_children, uint32_t* move_no,
+                   uint32_t* generation, uint32_t* actions, uint32_t* visits);
+
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
  * with the comma-separated vector, one line value1, one line value2; every line ends in '\n'.
