@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -94,6 +94,8 @@ SYMBOLS = [
     ("tafl_gselfplay_playout_cap_stats", _i32, [_vp, _P(TaflPlayoutCapStats)]),
     ("tafl_gselfplay_set_forced_playouts", _i32, [_vp, _P(TaflForcedPlayouts)]),
     ("tafl_gselfplay_forced_playouts_stats", _i32, [_vp, _P(TaflForcedPlayoutsStats)]),
+    ("tafl_gselfplay_set_solver", _i32, [_vp, _P(TaflSolver)]),
+    ("tafl_gselfplay_solver_stats", _i32, [_vp, _P(TaflSolverStats)]),
     ("tafl_pool_create", _i32, [_vp, _u32, _u32, _P(_vp)]),
     ("tafl_pool_destroy", _i32, [_vp]),
     ("tafl_pool_clear", _i32, [_vp]),

@@ -184,6 +184,17 @@ class TaflForcedPlayoutsStats(C.Structure):
     _fields_ = [("forced_sims", C.c_uint64), ("pruned_visits", C.c_uint64), ("pruned_children", C.c_uint64), ("full_moves", C.c_uint64)]
 
 
+class TaflSolver(C.Structure):
+    """tafl_solver: exact win/loss proofs in the searches of a guided self-play run (tafl_gselfplay_set_solver)."""
+    _fields_ = [("flags", C.c_uint32), ("_reserved", C.c_uint32 * 7)]
+
+
+class TaflSolverStats(C.Structure):
+    """tafl_solver_stats: what a run with the solver proved, skipped and pruned."""
+    _fields_ = [("root_won", C.c_uint64), ("root_lost", C.c_uint64), ("skipped_sims", C.c_uint64), ("nodes_won", C.c_uint64), ("nodes_lost", C.c_uint64),
+                ("pruned_visits", C.c_uint64), ("pruned_children", C.c_uint64), ("moves", C.c_uint64)]
+
+
 class TaflEpisodeOpts(C.Structure):
     """tafl_episode_opts: a guided self-play run in episodes (tafl_gselfplay_begin_episodes)."""
     _fields_ = [("id_stride", C.c_uint64), ("episode_moves", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
@@ -233,7 +244,7 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_mcts_stats": 200, "tafl_gmcts_stats": 64, "tafl_selfplay_opts": 32, "tafl_examples_stats": 32,
                   "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64, "tafl_match_opts": 32, "tafl_match_io": 72,
                   "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
-                  "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32,
+                  "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
                   "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
@@ -244,6 +255,7 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_episode_stats", TaflEpisodeStats), ("tafl_match_opts", TaflMatchOpts), ("tafl_match_io", TaflMatchIo),
                     ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats),
                     ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats),
+                    ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats),
                     ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 

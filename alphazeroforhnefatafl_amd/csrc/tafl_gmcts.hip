@@ -223,6 +223,19 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_forced(Consts<NL> C, G
                                                                   gs, nz, pc, fp);
     gstats_flush(gs, M.kind[g] == 1, stats);
 }
+// the round of a run with exact win/loss proofs (tafl_gselfplay_set_solver), kernels of their own once more.  They
+// go through the capped path and take the run's cap and forced playouts at run time: "every move full" without a cap, k == 0 without forcing
+template <int NL, int W, bool NOISE, bool EPISODES>
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_solver(Consts<NL> C, GuidedMem M, Quad* soa, const float* priors, const float* values, uint32_t A, double c_puct,
+                                                                 uint32_t n_sims, GSelfPlay sp, GEpisodes ep, SelfPlayRec rec, unsigned long long* stats, RootNoise nz, PlayoutCap pc,
+                                                                 ForcedPlayouts fp, SolverCfg sv) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    GuidedStats gs; gs.sims = gs.predicts = gs.terminal_hits = gs.faults = gs.depth = 0;
+    Guided<NL, W>::template selfplay_step_solver<NOISE, EPISODES>(M, g, soa, priors ? priors + (size_t)g * A : nullptr, values ? values[g] : 0.f, A, c_puct, n_sims, sp, ep, rec, C,
+                                                                  gs, nz, pc, fp, sv);
+    gstats_flush(gs, M.kind[g] == 1, stats);
+}
 // close and reopen, right after the round on the same stream: the lanes whose episode ended settle its examples, count it, take their
 // opening and wait with a fresh root (Guided::selfplay_reopen); every other lane leaves at its first load
 template <int NL, int W>
@@ -406,6 +419,28 @@ static int forced_check(const tafl_forced_playouts* cfg) {
 }
 
 extern "C" {
+
+int tafl_gselfplay_set_solver(tafl_batch* b, const tafl_solver* cfg) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_solver: null batch");
+    if (!cfg) { b->solver_set = false; return TAFL_OK; }
+    if (cfg->flags != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_solver: flags and reserved words must be 0");
+    for (uint32_t r : cfg->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_solver: flags and reserved words must be 0");
+    b->solver_set = true;
+    return TAFL_OK;
+}
+
+int tafl_gselfplay_solver_stats(tafl_batch* b, tafl_solver_stats* out) {
+    if (!b || !b->gsp_has || !b->gsp_solver_on || !out)
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_solver_stats: no run with the solver on this batch (tafl_gselfplay_set_solver, then a begin)");
+    tafl_ctx* c = b->ctx;
+    HIPCHK(hipSetDevice(c->device));
+    unsigned long long h[SV_COUNT];
+    HIPCHK(hipMemcpyAsync(h, b->gsp_solver_counters.p, sizeof h, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    out->root_won = h[SV_ROOT_WON]; out->root_lost = h[SV_ROOT_LOST]; out->skipped_sims = h[SV_SKIPPED_SIMS]; out->nodes_won = h[SV_NODES_WON];
+    out->nodes_lost = h[SV_NODES_LOST]; out->pruned_visits = h[SV_PRUNED_VISITS]; out->pruned_children = h[SV_PRUNED_CHILDREN]; out->moves = h[SV_MOVES];
+    return TAFL_OK;
+}
 
 int tafl_gselfplay_set_forced_playouts(tafl_batch* b, const tafl_forced_playouts* cfg) {
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_set_forced_playouts: null batch");
@@ -650,7 +685,18 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    if (b->gsp_forced_on) {                                     // forced playouts: rounds of their own (with or without a cap), then the reopen
+    if (b->gsp_solver_on) {                                     // exact proofs: rounds of their own (whatever the noise, the cap and the forcing), then the reopen
+        const bool nz = b->g_noise_on, ep = b->gsp_episodes;
+#define TAFL_SOLVER(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_solver<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap, b->gsp_forced, b->gsp_solver); })
+        if (ep) { if (nz) TAFL_SOLVER(true, true); else TAFL_SOLVER(false, true); }
+        else { if (nz) TAFL_SOLVER(true, false); else TAFL_SOLVER(false, false); }
+#undef TAFL_SOLVER
+        if (ep) {
+            HIPCHK(hipGetLastError());
+            dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
+        }
+    }
+    else if (b->gsp_forced_on) {                                // forced playouts: rounds of their own (with or without a cap), then the reopen
         const bool nz = b->g_noise_on, ep = b->gsp_episodes;
 #define TAFL_FORCED(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_forced<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap, b->gsp_forced); })
         if (ep) { if (nz) TAFL_FORCED(true, true); else TAFL_FORCED(false, true); }
@@ -737,7 +783,8 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     b->gsp_cap_on = b->cap_set; b->gsp_cap = PlayoutCap{};   // and the playout cap
     b->gsp_forced_on = b->forced_set; b->gsp_forced = ForcedPlayouts{};      // and forced playouts, whose rounds take a PlayoutCap in any case
-    if (b->cap_set || b->forced_set) {
+    b->gsp_solver_on = b->solver_set; b->gsp_solver = SolverCfg{};          // and the solver, whose rounds take a PlayoutCap and a ForcedPlayouts (k == 0: none) in any case
+    if (b->cap_set || b->forced_set || b->solver_set) {
         NEED(b->gsp_cap_counters, sizeof(unsigned long long) * CAP_COUNT);
         HIPCHK(hipMemsetAsync(b->gsp_cap_counters.p, 0, sizeof(unsigned long long) * CAP_COUNT, c->stream));
         if (b->cap_set) { b->gsp_cap.seed = b->cap_cfg.seed; b->gsp_cap.fast_sims = b->cap_cfg.fast_sims; b->gsp_cap.full_per_65536 = b->cap_cfg.full_per_65536; }
@@ -749,6 +796,11 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
         HIPCHK(hipMemsetAsync(b->gsp_forced_counters.p, 0, sizeof(unsigned long long) * FP_COUNT, c->stream));
         b->gsp_forced.k = b->forced_cfg.k;
         b->gsp_forced_counters.bind(b->gsp_forced.counters);
+    }
+    if (b->solver_set) {
+        NEED(b->gsp_solver_counters, sizeof(unsigned long long) * SV_COUNT);
+        HIPCHK(hipMemsetAsync(b->gsp_solver_counters.p, 0, sizeof(unsigned long long) * SV_COUNT, c->stream));
+        b->gsp_solver_counters.bind(b->gsp_solver.counters);
     }
     HIPCHK(hipMemsetAsync(b->gsp_plays.p, 0, sizeof(tafl_play) * (size_t)n * n_moves, c->stream));
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_init<t.NL, t.W>), c, n, t.CC, b->soa, b->gmem, b->gsp); });
@@ -816,6 +868,7 @@ int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, d
     for (uint32_t r : mo->_reserved) if (r != 0) return fail(TAFL_ERR_UNSUPPORTED, "tafl_match_opts: flags and reserved words must be 0");
     if (b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: root noise is set on the batch (tafl_gmcts_set_root_noise(NULL) first)");
     if (b->cap_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: a playout cap is set on the batch (tafl_gselfplay_set_playout_cap(NULL) first)");
+    if (b->solver_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: the solver is set on the batch (tafl_gselfplay_set_solver(NULL) first)");
     if (b->forced_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: forced playouts are set on the batch (tafl_gselfplay_set_forced_playouts(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     if (const int rc = gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b)) return rc;

@@ -21,6 +21,11 @@
 //
 // A guided self-play run records its examples and draws its plays with the functions of tafl_examples.hpp (example_append,
 // visit_draw, which own the example layout and the board encoding); this file only walks the root's edge block for them.
+//
+// Exact win/loss proofs (MCTS-Solver: include/taflhip.h tafl_solver) are compiled only into the SOLVER
+// instantiations (selfplay_step_solver).  A node's proof lives in bits 1-2 of GNode::expanded (a terminal's is its term code), the
+// losing-move / winning-move mark of an edge in bits 2-3 of GEdge::dir, mirrored there through pedge when the child is proven, so the
+// selection scan reads it from the record it loads anyway.  The functions without the flag are what they were.
 #pragma once
 #include "tafl_ops.hpp"
 
@@ -102,6 +107,12 @@ struct ForcedPlayouts {
     double k;                       // a visited root edge is forced while n * n < (k * p) * Ns
     unsigned long long* counters;   // [FP_COUNT]
 };
+// exact win/loss proofs (include/taflhip.h tafl_solver): an argument of the solver rounds alone
+enum { SV_ROOT_WON = 0, SV_ROOT_LOST, SV_SKIPPED_SIMS, SV_NODES_WON, SV_NODES_LOST, SV_PRUNED_VISITS, SV_PRUNED_CHILDREN, SV_MOVES, SV_COUNT };
+struct SolverCfg { unsigned long long* counters; };   // [SV_COUNT]
+enum { PROOF_NONE = 0, PROOF_WON = 1, PROOF_LOST = 2 };          // for the side to move at the node; GNode::expanded = expanded | proof << 1
+constexpr uint8_t kDirMask = 3u, kEdgeLosing = 4u, kEdgeWinning = 8u;   // GEdge::dir = dir | marks: the child is WON / the child is LOST
+enum { SL_SKIPPED = 0, SL_NODES_WON, SL_NODES_LOST, SL_COUNT };  // what one lane counts during one call of step_as
 // Dirichlet noise at the root (include/taflhip.h tafl_root_noise): what the search of one game mixes into Ps[root]
 struct RootNoise {
     double alpha, epsilon;
@@ -226,6 +237,39 @@ struct Guided {
         }
     }
 
+    // the solver rounds' backup (tafl_solver rule 3): the same walk, and behind every edge update the proof `cp` of the node just left
+    // is mirrored into that edge and may prove the parent: WON by a LOST child, LOST once every legal move has a WON child
+    static TAFL_HD void backup_solver(const GuidedMem& M, uint32_t g, uint32_t cur, double v, uint32_t cp, uint32_t* sl) {
+        while (cur != 0) {
+            const uint32_t par = M.hdr[(size_t)cur * M.G + g].parent;
+            GEdge* e = &M.edges[(size_t)g * M.edge_cap + M.pedge[(size_t)cur * M.G + g]];
+            if (e->n > 0) { e->q = ((double)e->n * e->q + v) / (double)(e->n + 1); e->n += 1; }
+            else { e->q = v; e->n = 1; }
+            GNode* ph = &M.hdr[(size_t)par * M.G + g];
+            ph->ns += 1;
+            if (cp != PROOF_NONE) {
+                e->dir = (uint8_t)(e->dir | (cp == PROOF_WON ? kEdgeLosing : kEdgeWinning));
+                uint32_t np = PROOF_NONE;
+                if ((ph->expanded >> 1) == PROOF_NONE) {
+                    if (cp == PROOF_LOST) np = PROOF_WON;
+                    else {
+                        const GEdge* pb = &M.edges[(size_t)g * M.edge_cap + ph->edge_base];
+                        bool all = true;
+                        for (uint32_t j = 0; j < ph->n_legal; ++j) all = all && (pb[j].dir & kEdgeLosing) != 0;
+                        if (all) np = PROOF_LOST;
+                    }
+                    if (np != PROOF_NONE) {
+                        ph->expanded = (uint8_t)(ph->expanded | (np << 1));
+                        if (par != 0) sl[np == PROOF_WON ? SL_NODES_WON : SL_NODES_LOST] += 1u;
+                    }
+                }
+                cp = np;
+            }
+            v = -v;
+            cur = par;
+        }
+    }
+
     // mcts.py:83-102 for the pending leaf, with the network's answer
     static TAFL_HD bool expand(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C) { return expand_as<false>(M, g, priors, A, C, nullptr); }
     // NOISE: when the leaf is node 0, P' = (1 - epsilon) P + epsilon eta (tafl_root_noise): the raw variates wait in the fresh edges' q
@@ -274,38 +318,53 @@ struct Guided {
                              const K& C, GuidedStats& gs, const RootNoise& nz) { step_as<true>(M, g, priors, value, A, c_puct, n_sims, C, gs, &nz); }
     // FORCED (the forced rounds, include/taflhip.h tafl_forced_playouts rule 1): in the search of a full move (`mix`) a visited edge of
     // node 0 with n * n < (k * p) * Ns scores +inf, so the first such edge is selected; *forced counts the simulations this happened to
-    template <bool NOISE, bool FORCED = false>
+    // SOLVER (the solver rounds, include/taflhip.h tafl_solver rules 1-5): terminals prove their parents, backup_solver carries the
+    // proofs up, the scan of a node skips its losing moves, and a proven root ends the search; sl[SL_COUNT] counts for this lane.  The
+    // forced-playouts argument is a run-time one there: k == 0 forces nothing
+    template <bool NOISE, bool FORCED = false, bool SOLVER = false>
     static TAFL_HD void step_as(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
-                                const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true, const ForcedPlayouts* fp = nullptr, uint32_t* forced = nullptr) {
+                                const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true, const ForcedPlayouts* fp = nullptr, uint32_t* forced = nullptr,
+                                uint32_t* sl = nullptr) {
         if (M.fault[g]) { M.kind[g] = 3; return; }
         uint32_t sims = M.sims_done[g];
         if (M.kind[g] == 1) {
             if (!priors || !expand_as<NOISE>(M, g, priors, A, C, nz, mix)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
             gs.predicts += 1;
-            backup(M, g, M.leaf[g], -(double)value);              // return -v (mcts.py:102) into the callers
+            if constexpr (SOLVER) backup_solver(M, g, M.leaf[g], -(double)value, PROOF_NONE, sl);
+            else backup(M, g, M.leaf[g], -(double)value);         // return -v (mcts.py:102) into the callers
             ++sims; gs.sims += 1;
         }
         M.kind[g] = 3;
         while (sims < n_sims) {
+            if constexpr (SOLVER) { if ((M.hdr[g].expanded >> 1) != PROOF_NONE) { sl[SL_SKIPPED] += n_sims - sims; sims = n_sims; break; } }   // rule 5
             uint32_t cur = 0; bool waiting = false;
             for (uint32_t depth = 0; depth <= M.node_cap; ++depth) {
                 const GNode h = M.hdr[(size_t)cur * M.G + g];
-                if (h.term) { backup(M, g, cur, -O::term_value(h.term)); gs.terminal_hits += 1; break; }   // mcts.py:79-81
-                if (!h.expanded) { M.leaf[g] = cur; M.kind[g] = 1; waiting = true; break; }               // mcts.py:83-85
+                if (h.term) {                                                                              // mcts.py:79-81
+                    if constexpr (SOLVER) backup_solver(M, g, cur, -O::term_value(h.term), h.term == 1 ? PROOF_WON : h.term == 2 ? PROOF_LOST : PROOF_NONE, sl);
+                    else backup(M, g, cur, -O::term_value(h.term));
+                    gs.terminal_hits += 1; break;
+                }
+                if (!(SOLVER ? h.expanded & 1 : h.expanded)) { M.leaf[g] = cur; M.kind[g] = 1; waiting = true; break; }   // mcts.py:83-85
                 gs.depth += 1;
                 GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
                 const double sq = sqrt((double)h.ns), sq0 = sqrt((double)h.ns + TAFL_MCTS_EPS);
                 double cur_best = -__builtin_inf(); int best = -1;
                 bool force = false; double kns = 0.0;
-                if constexpr (FORCED) { force = mix && cur == 0u; kns = (double)h.ns; }
+                if constexpr (FORCED) { force = mix && cur == 0u && (!SOLVER || fp->k > 0.0); kns = (double)h.ns; }
                 // eight edge records in flight at a time (the scan is bound by memory latency), evaluated in ascending action order
                 for (uint32_t j0 = 0; j0 < h.n_legal; j0 += 8) {
-                    double ep[8], eq[8]; uint32_t en[8];
-                    TAFL_UNROLL for (uint32_t t = 0; t < 8; ++t) { const GEdge* e = &eb[(j0 + t < h.n_legal) ? j0 + t : j0]; ep[t] = e->p; eq[t] = e->q; en[t] = e->n; }
+                    double ep[8], eq[8]; uint32_t en[8]; [[maybe_unused]] uint8_t ed[8];
+                    TAFL_UNROLL for (uint32_t t = 0; t < 8; ++t) {
+                        const GEdge* e = &eb[(j0 + t < h.n_legal) ? j0 + t : j0]; ep[t] = e->p; eq[t] = e->q; en[t] = e->n;
+                        if constexpr (SOLVER) ed[t] = e->dir;
+                    }
                     TAFL_UNROLL for (uint32_t t = 0; t < 8; ++t) {
                         double u = en[t] > 0 ? eq[t] + c_puct * ep[t] * sq / (double)(1 + en[t]) : c_puct * ep[t] * sq0;
                         if constexpr (FORCED) { if (force && en[t] > 0 && (double)en[t] * (double)en[t] < (fp->k * ep[t]) * kns) u = __builtin_inf(); }
-                        if (j0 + t < h.n_legal && u > cur_best) { cur_best = u; best = (int)(j0 + t); }
+                        bool open = j0 + t < h.n_legal;
+                        if constexpr (SOLVER) open = open && (ed[t] & kEdgeLosing) == 0;          // rule 4: a losing move is not selected
+                        if (open && u > cur_best) { cur_best = u; best = (int)(j0 + t); }
                     }
                 }
                 if (best < 0) { M.fault[g] = 1; gs.faults += 1; M.sims_done[g] = sims; return; }
@@ -315,7 +374,7 @@ struct Guided {
                     const uint32_t id = M.node_top[g];
                     if (id >= M.node_cap) { M.fault[g] = 1; gs.faults += 1; M.sims_done[g] = sims; return; }
                     S st; IO::load_rec(M.node_state + ((size_t)cur * M.G + g) * IO::QUADS, st);
-                    Move mv; mv.from = eb[best].from; mv.dir = eb[best].dir; mv.dist = eb[best].dist;
+                    Move mv; mv.from = eb[best].from; mv.dir = SOLVER ? eb[best].dir & kDirMask : eb[best].dir; mv.dist = eb[best].dist;
                     mv.to = (uint32_t)((int)mv.from + E::delta(mv.dir) * (int)mv.dist);
                     Moves<NL> nx;
                     E::apply(st, mv, C, nullptr, nx);
@@ -454,6 +513,34 @@ struct Guided {
         if (visits) TAFL_COUNT_ADD(&fp.counters[FP_PRUNED_VISITS], visits);
         if (children) TAFL_COUNT_ADD(&fp.counters[FP_PRUNED_CHILDREN], children);
     }
+    // Solver pruning (include/taflhip.h tafl_solver rule 6) of the finished root `h`, in place: a WON root keeps the visits of its first
+    // winning move alone; otherwise the losing moves give up theirs, provided a visited edge remains that is no losing move.  The marks
+    // leave the block with it, so everything after reads plain dir and n' as it reads n.  Counts the proven roots and what it took away.
+    static TAFL_HD void solver_prune(GEdge* eb, const GNode& h, const SolverCfg& sv) {
+        const uint32_t proof = h.expanded >> 1;
+        uint32_t visits = 0, children = 0;
+        if (proof == PROOF_WON) {
+            bool found = false;
+            for (uint32_t j = 0; j < h.n_legal; ++j) {
+                const uint32_t nj = eb[j].n;
+                if (!found && (eb[j].dir & kEdgeWinning)) { found = true; continue; }
+                if (nj != 0u) { eb[j].n = 0u; visits += nj; children += 1u; }
+            }
+        } else {
+            bool other = false;
+            for (uint32_t j = 0; j < h.n_legal; ++j) other = other || (!(eb[j].dir & kEdgeLosing) && eb[j].n != 0u);
+            if (other)
+                for (uint32_t j = 0; j < h.n_legal; ++j) {
+                    const uint32_t nj = eb[j].n;
+                    if ((eb[j].dir & kEdgeLosing) && nj != 0u) { eb[j].n = 0u; visits += nj; children += 1u; }
+                }
+        }
+        for (uint32_t j = 0; j < h.n_legal; ++j) { const uint8_t d = eb[j].dir; if (d & ~kDirMask) eb[j].dir = (uint8_t)(d & kDirMask); }
+        if (proof == PROOF_WON) TAFL_COUNT_ADD(&sv.counters[SV_ROOT_WON], 1);
+        if (proof == PROOF_LOST) TAFL_COUNT_ADD(&sv.counters[SV_ROOT_LOST], 1);
+        if (visits) TAFL_COUNT_ADD(&sv.counters[SV_PRUNED_VISITS], visits);
+        if (children) TAFL_COUNT_ADD(&sv.counters[SV_PRUNED_CHILDREN], children);
+    }
     // visit_draw (tafl_examples.hpp) over the root's edge block (one edge per LEGAL move, the unvisited ones in between): the index inside the block
     static TAFL_HD uint32_t selfplay_pick(const GEdge* eb, uint32_t n_legal, uint32_t N, uint32_t r) { return visit_draw(n_legal, N, r, [&](uint32_t j) { return eb[j].n; }); }
     // the start of a run for game g: a fresh root from its batch state; a game that is over makes no move
@@ -495,10 +582,13 @@ struct Guided {
     // FORCED: the round of a run with forced playouts (include/taflhip.h tafl_forced_playouts).  The search of a full move forces at
     // the root (step_as); when it is complete the visit counts of the root's edges are pruned in place (forced_prune: the block is dead
     // once the move is made), so the scan, the draw and the example below read n' as they read n
-    template <bool NOISE, bool EPISODES, bool CAP = false, bool FORCED = false>
+    // SOLVER: the round of a run with exact proofs (include/taflhip.h tafl_solver).  Every search, full or fast, proves what it can
+    // (step_as); when it is complete solver_prune edits the root's visit counts in place, before forced_prune, and the rest reads n'.
+    // Forced playouts are a run-time matter there (fp->k == 0: none)
+    template <bool NOISE, bool EPISODES, bool CAP = false, bool FORCED = false, bool SOLVER = false>
     static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                          const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep,
-                                         const PlayoutCap* pc = nullptr, const ForcedPlayouts* fp = nullptr) {
+                                         const PlayoutCap* pc = nullptr, const ForcedPlayouts* fp = nullptr, const SolverCfg* sv = nullptr) {
         uint32_t md = sp.moves_done[g];
         if (md & kGspStopped) return;
         // EPISODES: the game id and the first move of the lane's open episode (rec.move_base is 0); they hold for the whole call, a new
@@ -519,7 +609,14 @@ struct Guided {
         }
         // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
         for (;;) {
-            if constexpr (FORCED) {
+            if constexpr (SOLVER) {
+                uint32_t forced = 0, sl[SL_COUNT] = {0u, 0u, 0u};
+                step_as<NOISE, true, true>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced, sl);
+                if (forced) TAFL_COUNT_ADD(&fp->counters[FP_FORCED_SIMS], forced);
+                if (sl[SL_SKIPPED]) TAFL_COUNT_ADD(&sv->counters[SV_SKIPPED_SIMS], sl[SL_SKIPPED]);
+                if (sl[SL_NODES_WON]) TAFL_COUNT_ADD(&sv->counters[SV_NODES_WON], sl[SL_NODES_WON]);
+                if (sl[SL_NODES_LOST]) TAFL_COUNT_ADD(&sv->counters[SV_NODES_LOST], sl[SL_NODES_LOST]);
+            } else if constexpr (FORCED) {
                 uint32_t forced = 0;
                 step_as<NOISE, true>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced);
                 if (forced) TAFL_COUNT_ADD(&fp->counters[FP_FORCED_SIMS], forced);
@@ -527,7 +624,8 @@ struct Guided {
             if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
             if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
             const GNode h = M.hdr[g];
-            if constexpr (FORCED) { if (full && h.expanded) forced_prune(&M.edges[(size_t)g * M.edge_cap + h.edge_base], h, c_puct, *fp); }
+            if constexpr (SOLVER) { if (h.expanded) solver_prune(&M.edges[(size_t)g * M.edge_cap + h.edge_base], h, *sv); }
+            if constexpr (FORCED) { if (full && h.expanded && (!SOLVER || fp->k > 0.0)) forced_prune(&M.edges[(size_t)g * M.edge_cap + h.edge_base], h, c_puct, *fp); }
             const GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
             uint32_t best = 0, pick = 0, total = 0, m = 0;
             if (h.expanded)
@@ -552,7 +650,8 @@ struct Guided {
             Move mv; mv.from = pe.from; mv.dir = pe.dir; mv.dist = pe.dist; mv.to = 0;
             sp.plays[(size_t)md * M.G + g] = O::to_play(mv);
             if constexpr (CAP) TAFL_COUNT_ADD(&pc->counters[full ? CAP_FULL : CAP_FAST], 1);
-            if constexpr (FORCED) { if (full) TAFL_COUNT_ADD(&fp->counters[FP_FULL_MOVES], 1); }
+            if constexpr (FORCED) { if (full && (!SOLVER || fp->k > 0.0)) TAFL_COUNT_ADD(&fp->counters[FP_FULL_MOVES], 1); }
+            if constexpr (SOLVER) TAFL_COUNT_ADD(&sv->counters[SV_MOVES], 1);
             md += 1u;
             if constexpr (EPISODES) {
                 if (md >= sp.n_moves) { sp.moves_done[g] = md | kGspStopped; return; }      // the budget is used up: the episode stays open
@@ -575,6 +674,14 @@ struct Guided {
                                              const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz, const PlayoutCap& pc,
                                              const ForcedPlayouts& fp) {
         selfplay_step_as<NOISE, EPISODES, true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc, &fp);
+    }
+    // the solver rounds (tafl_gselfplay_set_solver): through the capped path as the forced rounds are, with the cap and the forced
+    // playouts of the run at run time - "every move full" without a cap, k == 0 without forced playouts
+    template <bool NOISE, bool EPISODES>
+    static TAFL_HD void selfplay_step_solver(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
+                                             const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise& nz, const PlayoutCap& pc,
+                                             const ForcedPlayouts& fp, const SolverCfg& sv) {
+        selfplay_step_as<NOISE, EPISODES, true, true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc, &fp, &sv);
     }
     // a fresh root that waits for its evaluation: what `step` leaves when it meets the unexpanded root of an ongoing game
     static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) { init_game(M, g, root); M.kind[g] = 1; }

@@ -248,6 +248,11 @@ struct tafl_batch {
     bool forced_set = false, gsp_forced_on = false;
     tafl_forced_playouts forced_cfg = {}; ForcedPlayouts gsp_forced = {};
     DevBuf gsp_forced_counters;
+    // exact win/loss proofs (tafl_gselfplay_set_solver): the setting, and what that run latched (gsp_solver_on: its rounds are the solver
+    // ones; its eight counters)
+    bool solver_set = false, gsp_solver_on = false;
+    SolverCfg gsp_solver = {};
+    DevBuf gsp_solver_counters;
     // subtree reuse (TAFL_MCTS_FLAG_KEEP_TREE): the arena holds trees rooted at the current batch states (*_tree_live); the second edge
     // arena and the id map of a re-root; a small read-back buffer
     bool tree_live = false, g_tree_live = false;

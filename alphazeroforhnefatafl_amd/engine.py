@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -489,6 +489,23 @@ class GameBatch:
         (tafl_gselfplay_forced_playouts_stats)."""
         st = TaflForcedPlayoutsStats()
         check(lib().tafl_gselfplay_forced_playouts_stats(self._h, C.byref(st)))
+        return st
+
+    # -- exact win/loss proofs in the searches of a guided self-play run (include/taflhip.h tafl_solver) ---------------------------
+    def set_solver(self):
+        """Every later gselfplay_begin / gselfplay_begin_episodes run (latched at the begin) back-propagates win/loss proofs beside the
+        values: its searches skip moves that lose, end once the root is decided, and keep proven losses out of the play and the example."""
+        cfg = TaflSolver(0)
+        check(lib().tafl_gselfplay_set_solver(self._h, C.byref(cfg)))
+
+    def clear_solver(self):
+        check(lib().tafl_gselfplay_set_solver(self._h, None))
+
+    def solver_stats(self) -> TaflSolverStats:
+        """Proven roots and nodes, skipped simulations, pruned visits and children and the moves of the run that is open, or was last
+        (tafl_gselfplay_solver_stats)."""
+        st = TaflSolverStats()
+        check(lib().tafl_gselfplay_solver_stats(self._h, C.byref(st)))
         return st
 
     def root_noise_eval(self, alpha: float, epsilon: float, seed: int, game_id_base: int = 0, move_no: int = 0, out_device_ptr: int | None = None):

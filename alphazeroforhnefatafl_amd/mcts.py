@@ -36,6 +36,8 @@ class MCTSArgs:
     capSeed: int = 0
     # forced playouts and policy target pruning of a guided self-play run (include/taflhip.h tafl_forced_playouts); 0: off
     forcedPlayoutsK: float = 0.0
+    # exact win/loss proofs in the searches of a guided self-play run (include/taflhip.h tafl_solver)
+    solver: bool = False
 
 
 def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
@@ -60,6 +62,14 @@ def apply_forced_playouts(batch: GameBatch, args: MCTSArgs):
         batch.set_forced_playouts(args.forcedPlayoutsK)
     else:
         batch.clear_forced_playouts()
+
+
+def apply_solver(batch: GameBatch, args: MCTSArgs):
+    """The batch's solver setting as `args` asks for it: set, or cleared."""
+    if args.solver:
+        batch.set_solver()
+    else:
+        batch.clear_solver()
 
 
 _M32 = 0xFFFFFFFF

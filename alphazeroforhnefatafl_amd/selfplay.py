@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi import TaflState
 from .engine import Examples, GameBatch
-from .mcts import MCTSArgs, apply_forced_playouts, apply_playout_cap, apply_root_noise
+from .mcts import MCTSArgs, apply_forced_playouts, apply_playout_cap, apply_root_noise, apply_solver
 
 
 class MatchResult:
@@ -51,10 +51,13 @@ def play_match(batch: GameBatch, nets, args: MCTSArgs, lane_moves: int, *, examp
         raise ValueError("play_match: a match takes no playout cap (args.fastSims must be 0)")
     if args.forcedPlayoutsK:
         raise ValueError("play_match: a match takes no forced playouts (args.forcedPlayoutsK must be 0)")
+    if args.solver:
+        raise ValueError("play_match: a match takes no solver (args.solver must be False)")
     n = batch.n
     batch.clear_root_noise()
     batch.clear_playout_cap()
     batch.clear_forced_playouts()
+    batch.clear_solver()
     batch.gmatch_begin(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                        temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings, swap=swap)
     ptrs = None
@@ -120,10 +123,12 @@ def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     args.fastSims > 0 turns on playout cap randomization (include/taflhip.h tafl_playout_cap): a move is full - args.numMCTSSims
     simulations, noise, recorded - with probability args.fullMoveProb, otherwise args.fastSims simulations, no noise, not recorded.
     args.forcedPlayoutsK > 0 turns on forced playouts and policy target pruning in the full moves (include/taflhip.h
-    tafl_forced_playouts; batch.forced_playouts_stats() counts them)."""
+    tafl_forced_playouts; batch.forced_playouts_stats() counts them).  args.solver turns on exact win/loss proofs in every search
+    (include/taflhip.h tafl_solver; batch.solver_stats() counts them)."""
     apply_root_noise(batch, args)
     apply_playout_cap(batch, args)
     apply_forced_playouts(batch, args)
+    apply_solver(batch, args)
     batch.gselfplay_begin(examples, max_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=args.game_id_base,
                           sample_seed=sample_seed, temp_moves=temp_moves, move_base=move_base)
     waiting = batch.gselfplay_step()
@@ -151,11 +156,12 @@ def play_guided_selfplay(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     (nnet, device and buffers as in play_guided_episodes); then Examples.finalize settles the open tails.  args.dirichletEpsilon > 0
     mixes root noise keyed by the episode's game id and move number; args.fastSims > 0 turns on playout cap randomization as in
     play_guided_episodes (mcts.playout_cap_is_full tells which moves were full; batch.playout_cap_stats() counts them), and
-    args.forcedPlayoutsK > 0 forced playouts with policy target pruning in the full moves.  Returns
+    args.forcedPlayoutsK > 0 forced playouts with policy target pruning in the full moves, args.solver exact win/loss proofs.  Returns
     (episodes closed or cut per lane, TaflEpisodeStats, examples recorded in all, (dropped, overflowed))."""
     apply_root_noise(batch, args)
     apply_playout_cap(batch, args)
     apply_forced_playouts(batch, args)
+    apply_solver(batch, args)
     batch.gselfplay_begin_episodes(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                                    temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings)
     waiting = batch.gselfplay_step()

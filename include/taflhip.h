@@ -819,6 +819,54 @@ typedef struct tafl_forced_playouts_stats { uint64_t forced_sims, pruned_visits,
 int tafl_gselfplay_set_forced_playouts(tafl_batch* b, const tafl_forced_playouts* cfg);
 int tafl_gselfplay_forced_playouts_stats(tafl_batch* b, tafl_forced_playouts_stats* out);
 
+/* ---- exact win/loss proofs in guided self-play: MCTS-Solver -----------------------------------------------------------
+ * The game is decided by sudden tactics, and the one thing a search knows exactly is a finished game.  Without this setting a terminal
+ * node is a value of +-1 averaged into a running mean; with it the search back-propagates PROOFS beside the values (Winands et al. 2008),
+ * stops selecting moves that lose, ends as soon as its root is decided and keeps proven losses out of the play and the policy target.
+ * Build-defined.  Off by default; with it off nothing in this header behaves differently.
+ *
+ * Every node has a proof: NONE, WON or LOST, for the side to move at that node.  All other arithmetic stays bit for bit: priors, PUCT,
+ * the running-mean backup, the noise, the cap classes, the forcing.
+ *   1 terminals    a node is created on the first visit of its edge.  If its game is over with a winner it is WON when the winner is the
+ *                  side to move there, otherwise LOST; the backed-up value is -+term_value as without the setting.  A draw proves nothing.
+ *   2 edges        an edge of node s is a LOSING MOVE once its child is WON, and a WINNING MOVE once its child is LOST.
+ *   3 propagation  in the backup walk of every simulation, after the edge's Q/N update.  At each node s on the path whose proof is NONE:
+ *                  s becomes WON if the child just left is LOST; s becomes LOST if that child is WON and every legal move of s has a child
+ *                  that is WON (an unvisited edge has no child, so it blocks this).  The walk goes on to the root.
+ *   4 selection    in a node whose proof is NONE the scan skips losing moves.  Everything else is unchanged: ascending action order, strict
+ *                  >, and the +inf of tafl_forced_playouts rule 1 only for edges that are not skipped.  Such a node has at least one edge
+ *                  that is no losing move and has no winning move.  A node whose proof is not NONE is never descended into (rule 5).
+ *   5 the end      before each simulation: if the root's proof is not NONE the search of this move is complete - sims_done = n_sims,
+ *                  kind = 3 - and the simulations not run are counted in skipped_sims (a fast move of a capped run counts from its own
+ *                  n_sims - fast_sims).
+ *   6 pruning      when the search of a move is complete, before rule 2 of tafl_forced_playouts and before the play is chosen; n' from n:
+ *                  root WON: w = the first winning move in ascending action order, n'_w = n_w, every other n' = 0;
+ *                  otherwise n' = 0 for every losing move, provided some edge that is not a losing move has n > 0; if none has (the
+ *                  root is LOST, or only losing moves were visited) n' = n everywhere.
+ *                  Afterwards everything uses n', exactly as rule 3 of tafl_forced_playouts says for its n': the forced-playouts pruning,
+ *                  the children count and overflow test of the example, the stored (action | n' << 16) words, N, the draw for
+ *                  M < temp_moves and the first-maximum pick.  So a WON root plays w whatever temp_moves is and records a one-entry
+ *                  policy.  Fast moves are pruned too; they record nothing, as ever.
+ * The proof of a node and the mark of an edge live in spare bits of the search arena; its sizes are those of a run without the setting.
+ *
+ * tafl_gselfplay_set_solver stores the setting on the batch (cfg == NULL: off).  tafl_gselfplay_begin and tafl_gselfplay_begin_episodes
+ *   latch it: a change during a run takes effect at the next begin.  Non-zero flags or _reserved: TAFL_ERR_UNSUPPORTED (the setting is
+ *   left as it was).  While it is set tafl_gmatch_begin fails with TAFL_ERR_UNSUPPORTED.  The lock-step tafl_gmcts_* searches (their
+ *   getters included) and the rollout-mode tafl_selfplay_record ignore the setting.  It composes with root noise, the playout cap and
+ *   forced playouts in every combination those allow.
+ * tafl_gselfplay_solver_stats: root_won / root_lost = searches that were complete with a WON / LOST root, skipped_sims = simulations
+ *   rule 5 did not run (tafl_gmcts_stats' sims + skipped_sims = the budgets of the searches), nodes_won / nodes_lost = non-root nodes that
+ *   rule 3 marked (terminals are not counted), pruned_visits = sum (n - n') and pruned_children = edges with n > 0 and n' == 0 of rule 6,
+ *   moves = moves made; counted on the device; valid from the begin until the next tafl_gselfplay_begin / _begin_episodes on the batch
+ *   (also after tafl_gselfplay_end), TAFL_ERR_INVALID_ARG when that run latched no setting.
+ * Not offered: proofs in lock-step searches, matches or rollout-mode self-play, subtree reuse, draw proofs, backing up proven values in
+ *   place of the mean, a one-ply win check at expansion, transposition tables. */
+typedef struct tafl_solver { uint32_t flags; uint32_t _reserved[7]; } tafl_solver;            /* 32 bytes, all 0 */
+typedef struct tafl_solver_stats { uint64_t root_won, root_lost, skipped_sims, nodes_won, nodes_lost,
+                                   pruned_visits, pruned_children, moves; } tafl_solver_stats;  /* 64 bytes */
+int tafl_gselfplay_set_solver(tafl_batch* b, const tafl_solver* cfg);    /* NULL: off */
+int tafl_gselfplay_solver_stats(tafl_batch* b, tafl_solver_stats* out);
+
 /* ---- training pool: a window over finished examples, sampled on the device ------------------------------------------
  * The piece between "self-play wrote examples" and "the trainer takes a minibatch": a fixed-capacity ring of finished examples in HBM that
  * outlives the tafl_examples objects it was filled from (alpha-zero-general keeps the examples of the last N iterations and trains on
