@@ -190,7 +190,7 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK) void k_rollout(Consts<NL> Ca
     if (g >= n) return;
     DState<NL> st; load_batch_state<NLS, WS, NL, W>(soa, n, g, C.n, st);
     tafl_rollout_result r;
-    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut);
+    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut, KernelPlayout());
     out[g] = r;
 }
 

@@ -74,6 +74,40 @@ struct StepOut {
     uint32_t n_captures;
 };
 
+// ---- what a playout leaves behind (tafl_fast.hpp: Fast::rollout / Fast::ply_of) ------------------------------------------------------
+// KeepState:  the state is the game's state after the playout, field by field (random_advance plays in place; the default everywhere).
+// ValueOnly:  the caller reads value / reason / plies only (the search's playouts, k_rollout on its copy).  The repetition tracker then
+//             lives in a PlayoutTrack beside the state; rep / reps / the mid-pair flags of the state stay as they came in.
+struct KeepState { static constexpr bool packed = false; };
+struct ValueOnly { static constexpr bool packed = true; };
+// what the playout kernels use: -DTAFL_PLAYOUT_KEEP builds them on the keeping path (tools/rollout_bench.hip, tools/opclass_sections.hip)
+#if defined(TAFL_PLAYOUT_KEEP)
+using KernelPlayout = KeepState;
+#else
+using KernelPlayout = ValueOnly;
+#endif
+
+// The repetition tracker of a value-only playout.
+//   older[s], newer[s]   the records of side s's last two plays.  A record is from | to << 8 (tile indices of the state's own layout,
+//            < NL * 32 <= 256) of a play WITHOUT capture, and 0 for "can never match": None, a play that captured, an entry of the other
+//            side, an entry that is no slide on this board.  0 is no play's record (from != to).
+//            Exactness: for a slide on the board the map (from_row, from_col, axis, disp) -> (from, to) with from = from_row * W + from_col
+//            and to = from + disp * (axis ? 1 : W) is a bijection onto the pairs of distinct tiles on one line (row and column of `from`
+//            are its quotient and remainder by W, the axis is the line the two tiles share - unique as from != to - and disp the signed
+//            distance along it).  TAFL_REP_PACK words of one side with the captured bit clear are therefore equal iff their records are,
+//            and Engine::track's hit test `!captured && rec == rep[0]` can only hold for an entry with the mover's side bit and a clear
+//            captured bit: `!captured && record == older record of the mover` is the same test.
+//   cnt[s]   2 * reps + 1 - mid_pair of side s (>= 1), reps counted without the saturation at 0xFFFF.  Engine::track on a hit: mid clear ->
+//            reps + 1 and mid set; mid set -> mid clear: either way cnt + 1.  On a miss reps = 0 and mid clear: cnt = 1.  So one add and
+//            one select keep both.  reps = cnt >> 1; the saturated counter of the state is min(reps, 0xFFFF) as long as no miss
+//            intervenes (a miss resets both), and the only reader, `reps >= n_repetitions`, is n <= 0xFFFF && cnt >= 2 n.
+//            cnt starts below 2^17 and gains at most one every second ply of a 32-bit ply count: it cannot wrap.
+struct PlayoutTrack {
+    uint32_t older[2], newer[2], cnt[2];
+    // has `side` reached n_repetitions?
+    TAFL_HD bool reached(uint32_t side, uint32_t n) const { return n <= 0xFFFFu && cnt[side] >= 2u * n; }
+};
+
 template <int NL, int W>
 struct Engine {
     using B = Bits<NL>;
@@ -579,6 +613,35 @@ struct Engine {
         st.rep[0] = st.rep[1]; st.rep[1] = st.rep[2]; st.rep[2] = st.rep[3]; st.rep[3] = rec;
     }
 
+    // The same on a PlayoutTrack (value-only playouts): hit, mid-pair and counter rules are those of track() above.
+    template <uint32_t MOVER>
+    static TAFL_HD void track_value(PlayoutTrack& t, const Move& m, bool captured) {
+        const uint32_t rec = m.from | (m.to << 8);
+        const bool hit = !captured && rec == t.older[MOVER];
+        t.cnt[MOVER] = hit ? t.cnt[MOVER] + 1u : 1u;
+        t.older[MOVER] = t.newer[MOVER]; t.newer[MOVER] = captured ? 0u : rec;
+    }
+    // ring entry -> record of `side` (PlayoutTrack): 0 unless the entry is exactly the TAFL_REP_PACK word of a slide of `side` on this
+    // board that did not capture
+    static TAFL_HD uint32_t record_of(uint32_t e, uint32_t side, const K& C) {
+        const uint32_t fr = (e >> 16) & 0xFFu, fc = (e >> 8) & 0xFFu, horiz = (e >> 28) & 1u;
+        const int disp = (int)(int8_t)(uint8_t)(e & 0xFFu);
+        const uint32_t line = (uint32_t)((int)(horiz ? fc : fr) + disp);                 // wraps to >= n when off the board
+        const bool ok = (e & 0xEF000000u) == (0x80000000u | (side << 30)) && fr < C.n && fc < C.n && disp != 0 && line < C.n;
+        const uint32_t from = mul24(fr, (uint32_t)W) + fc, to = horiz ? mul24(fr, (uint32_t)W) + line : mul24(line, (uint32_t)W) + fc;
+        return ok ? (from | (to << 8)) : 0u;
+    }
+    // Entry conversion, once per playout.  Ring entry i (oldest first) is compared only by ply i of the playout, made by side
+    // start_side ^ (i & 1): entries 0 and 2 become the older / newer record of the side to move, 1 and 3 those of the other side.
+    static TAFL_HD void track_in(const S& st, const K& C, PlayoutTrack& t) {
+        const uint32_t s0 = st.flags & TAFL_F_SIDE, s1 = s0 ^ 1u;
+        const uint32_t o0 = record_of(st.rep[0], s0, C), n0 = record_of(st.rep[2], s0, C);
+        const uint32_t o1 = record_of(st.rep[1], s1, C), n1 = record_of(st.rep[3], s1, C);
+        t.older[0] = s0 ? o1 : o0; t.older[1] = s0 ? o0 : o1; t.newer[0] = s0 ? n1 : n0; t.newer[1] = s0 ? n0 : n1;
+        t.cnt[0] = 2u * (st.reps & 0xFFFFu) + ((st.flags & TAFL_F_AMID) ? 0u : 1u);
+        t.cnt[1] = 2u * (st.reps >> 16) + ((st.flags & TAFL_F_DMID) ? 0u : 1u);
+    }
+
     // ---- do_valid_play (logic.rs:782-820) + get_game_outcome (:702-771) ---------------------------------------------
     // Split in three so that the fast playout engine (tafl_fast.hpp) can slot its own move generator in between:
     //   apply_pre      move the piece, captures, removal, repetition tracker             (logic.rs:787-799)
@@ -592,7 +655,8 @@ struct Engine {
     // the same with the mover handed in: `mover` must equal st.flags & TAFL_F_SIDE.  The playout loop of tafl_fast.hpp passes a
     // compile-time constant (its two half-iterations each serve one side), which folds every `mover ? a : b` below and in captures().
     // lut: how a run-time tile index becomes its one-bit mask (tafl_tables.hpp); the default is the computed bit_at
-    template <class L = IdxComputed<NL>>
+    // TRACK = false (value-only playouts): the tracker and plays_since_capture are not kept in the state; the caller runs track_value()
+    template <class L = IdxComputed<NL>, bool TRACK = true>
     static TAFL_HD void apply_pre(S& st, const Move& m, const K& C, ApplyCtx& ax, const uint32_t mover, const L& lut = L()) {
         const B fbit = lut.bit(m.from), tbit = lut.bit(m.to);
         const bool mover_is_king = mover && m.from == king_sq(st, C);
@@ -609,14 +673,18 @@ struct Engine {
         ax.king_captured = mover == 0 && king_sq(st, C) != TAFL_NO_SQ && test(caps, king_sq(st, C));
         st.att = andn(st.att, caps); st.def = andn(st.def, caps);
         ax.ncap = popc(caps); ax.caps = caps; ax.mover = mover; ax.mover_is_king = mover_is_king; ax.tbit = tbit;
+        if constexpr (TRACK) {
 #ifndef TAFL_ABLATE_TRACK
-        track(st, mover, m, ax.ncap != 0);
+            track(st, mover, m, ax.ncap != 0);
 #endif
-        if (ax.ncap == 0) st.psc += 1;
+            if (ax.ncap == 0) st.psc += 1;
+        }
     }
     // skip_enclosure / skip_fort: the caller has PROVED that the enclosure win / the exit fort cannot apply (see tafl_fast.hpp); never
     // set otherwise.
-    static TAFL_HD Outcome outcome_early(const S& st, const ApplyCtx& ax, const K& C, bool skip_enclosure, bool skip_fort = false) {
+    // REPS_GIVEN (value-only playouts): reps_reached says whether the mover's repetition count has reached n_repetitions; st.reps is not read
+    template <bool REPS_GIVEN = false>
+    static TAFL_HD Outcome outcome_early(const S& st, const ApplyCtx& ax, const K& C, bool skip_enclosure, bool skip_fort = false, bool reps_reached = false) {
         Outcome o; o.over = false; o.status = TAFL_STATUS_ONGOING; o.reason = 0; o.winner = 0;
         const uint32_t mover = ax.mover;
         const B other = sel(mover != 0, st.att, st.def) & C.board;
@@ -654,8 +722,10 @@ struct Engine {
 #endif
         }
         if (!o.over && C.rules.has_repetition_rule) {
-            const uint32_t reps = mover ? (st.reps >> 16) : (st.reps & 0xFFFFu);
-            if (reps >= C.rules.n_repetitions) {
+            bool reached;
+            if constexpr (REPS_GIVEN) reached = reps_reached;
+            else { const uint32_t reps = mover ? (st.reps >> 16) : (st.reps & 0xFFFFu); reached = reps >= C.rules.n_repetitions; }
+            if (reached) {
                 if (C.rules.rep_is_loss) { o.status = TAFL_STATUS_WIN; o.reason = TAFL_WIN_REPETITION; o.winner = mover ^ 1u; }
                 else { o.status = TAFL_STATUS_DRAW; o.reason = TAFL_DRAW_REPETITION; }
                 o.over = true;

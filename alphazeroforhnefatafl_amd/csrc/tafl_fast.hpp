@@ -248,8 +248,10 @@ struct Fast {
     // attacker's play, the king-escape and exit-fort tests only behind a defender's, the king-capture block only in the attacker's half.
     // 64 games share an instruction stream: before, a wave paid for both sides' code on every ply.
     // g: plays of MOVER on entry, of the other side on exit; rk: the ply's RNG word before mixing (sk + ply * 0x85EBCA77, kept incrementally).
-    template <uint32_t MOVER, class L = IdxComputed<NL>>
-    static TAFL_HD void ply_of(S& st, B& attT, B& defT, Gen& g, uint32_t& rk, const K& C, const F& fc, const L& lut = L()) {
+    // P / vt: what the playout leaves behind (tafl_core.hpp).  KeepState: the state, field by field, vt is not touched.  ValueOnly: the
+    // repetition tracker lives in vt; rep, reps and the mid-pair flags of st are neither read nor written.
+    template <uint32_t MOVER, class L = IdxComputed<NL>, class P = KeepState>
+    static TAFL_HD void ply_of(S& st, B& attT, B& defT, Gen& g, uint32_t& rk, const K& C, const F& fc, const L& lut, PlayoutTrack& vt) {
         TAFL_PROF_COUNT(31); TAFL_STAT_HIT(31);
         TAFL_PROF_BEGIN(10); TAFL_PROF_SPLIT(10); TAFL_PROF_END(11);      // two empty sections: the cost of a mark
         TAFL_PROF_BEGIN(0);
@@ -258,7 +260,10 @@ struct Fast {
         const Move m = pick(st, attT, defT, g, idx, C);
         TAFL_PROF_SPLIT(0);
         typename E::ApplyCtx ax;
-        E::apply_pre(st, m, C, ax, MOVER, lut);
+        E::template apply_pre<L, !P::packed>(st, m, C, ax, MOVER, lut);
+#ifndef TAFL_ABLATE_TRACK
+        if constexpr (P::packed) E::template track_value<MOVER>(vt, m, ax.ncap != 0);
+#endif
         TAFL_PROF_SPLIT(4);
         // T layout upkeep: the move, the custodial captures (V+- are +-1 here, H+- are +-W), then whatever else was
         // captured (shieldwall, king, Linnaean: rare)
@@ -286,14 +291,22 @@ struct Fast {
         bool skip_encl = false, skip_fort = false;
         if constexpr (MOVER == 0) skip_encl = C.rules.enclosure_win == TAFL_ENCL_WITHOUT_EDGE_ACCESS && (g.edge_hit || any(st.def & C.edge));
         else if (C.rules.exit_fort) { skip_fort = !fort_candidate(st, attT, defT, C); if (!skip_fort) TAFL_STAT_HIT(13); }
-        const typename E::Outcome o = E::outcome_early(st, ax, C, skip_encl, skip_fort);
+        typename E::Outcome o;
+        if constexpr (P::packed) o = E::template outcome_early<true>(st, ax, C, skip_encl, skip_fort, vt.reached(MOVER, C.rules.n_repetitions));
+        else o = E::outcome_early(st, ax, C, skip_encl, skip_fort);
         E::apply_finish(st, ax, o, o.over ? 1u : g.total, C);
         TAFL_PROF_END(7);
     }
+    template <uint32_t MOVER, class L = IdxComputed<NL>>
+    static TAFL_HD void ply_of(S& st, B& attT, B& defT, Gen& g, uint32_t& rk, const K& C, const F& fc, const L& lut = L()) {
+        PlayoutTrack none{};
+        ply_of<MOVER, L, KeepState>(st, attT, defT, g, rk, C, fc, lut, none);
+    }
 
-    // one seeded uniform-random playout; identical results to Engine::rollout
-    template <class L = IdxComputed<NL>>
-    static TAFL_HD void rollout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& res, const L& lut = L()) {
+    // one seeded uniform-random playout; identical results to Engine::rollout.
+    // P = ValueOnly: `res` alone is the result; st comes back without its repetition tracker (rep, reps, mid-pair flags as they came in).
+    template <class L = IdxComputed<NL>, class P = KeepState>
+    static TAFL_HD void rollout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& res, const L& lut = L(), P = P()) {
         const F fc = make_fast_consts<NL>(C);
         const uint32_t start_side = st.flags & TAFL_F_SIDE;
         B attT, defT;
@@ -301,6 +314,8 @@ struct Fast {
         Gen g;
         if (TAFL_F_STATUS(st.flags) == TAFL_STATUS_ONGOING) gen(st, attT, defT, start_side, C, fc, g);
         else { TAFL_UNROLL for (int d = 0; d < 4; ++d) { g.r[d] = bz<NL>(); g.cnt[d] = 0; } g.total = 0; g.edge_hit = false; }
+        PlayoutTrack vt{};
+        if constexpr (P::packed) E::track_in(st, C, vt);
         uint32_t ply = 0, rk = sk; bool stuck = false;
         // a playout goes on while the game is on, the cap is not reached and the side to move has a play (else: stuck)
         auto goes_on = [&]() -> bool {
@@ -311,9 +326,9 @@ struct Fast {
         bool active = goes_on();
         bool skip_first = start_side != 0;     // a playout that starts with a defender's play sits out the first (attacker's) half
         while (wave_any(active)) {
-            if (active && !skip_first) { ply_of<0>(st, attT, defT, g, rk, C, fc, lut); ++ply; active = goes_on(); }
+            if (active && !skip_first) { ply_of<0, L, P>(st, attT, defT, g, rk, C, fc, lut, vt); ++ply; active = goes_on(); }
             skip_first = false;
-            if (active) { ply_of<1>(st, attT, defT, g, rk, C, fc, lut); ++ply; active = goes_on(); }
+            if (active) { ply_of<1, L, P>(st, attT, defT, g, rk, C, fc, lut, vt); ++ply; active = goes_on(); }
         }
         E::finish_rollout(st, start_side, ply, stuck, res);
     }

@@ -171,7 +171,7 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK, TAFL_ROLLOUT_WAVES) void k_m
     TAFL_UNROLL for (uint32_t t = 1; t < TAFL_MCTS_MAX_SLOTS; ++t) { const bool ge = i >= pre[t]; cls = ge ? t : cls; off = ge ? pre[t] : off; }
     const uint32_t e = has ? work[(size_t)cls * stride + (i - off)] : 0u;
     const uint32_t j = e >> 27, g = e & 0x07FFFFFFu;
-    if (has) Ops<NL, W>::mcts_slot_rollout(M, j, g, seed, base + g, sim_offset, max_plies, C, lut);
+    if (has) Ops<NL, W>::mcts_slot_rollout(M, j, g, seed, base + g, sim_offset, max_plies, C, lut, KernelPlayout());
     if ((threadIdx.x & 63) == 0) atomicAdd(&stats[ST_EXEC], (unsigned long long)__popcll(__ballot(has)));
 }
 
@@ -208,7 +208,7 @@ __global__ TAFL_KATTR __launch_bounds__(TAFL_BLOCK, TAFL_ROLLOUT_WAVES) void k_m
         const bool work = rg < M.G && rj < M.spec_k && M.spec_kind[(size_t)rj * M.G + rg] == 1;
         const unsigned long long wb = __ballot(work);
         if (wb == 0ull) continue;
-        if (work) Ops<NL, W>::mcts_slot_rollout(M, rj, rg, seed, base + rg, sim_offset, max_plies, C, lut);
+        if (work) Ops<NL, W>::mcts_slot_rollout(M, rj, rg, seed, base + rg, sim_offset, max_plies, C, lut, KernelPlayout());
         executed += (uint32_t)__popcll(wb);
         __threadfence();
     }

@@ -337,15 +337,17 @@ struct Ops {
     // playout dispatcher: the fast two-layout engine whenever the rules allow it (tafl_fast.hpp), else the generic one.
     // `force_generic` exists for the differential tests only.
     // `lut`: the index policy of the fast engine's ply (tafl_tables.hpp): tables in LDS in the playout kernels, computed everywhere else.
-    template <class L = IdxComputed<NL>>
-    static TAFL_HD void playout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& r, bool force_generic = false, const L& lut = L()) {
-        if (fast_ok<NL>(C) && !force_generic) Fast<NL, W>::rollout(st, sk, max_plies, C, r, lut);
+    // `P`: KeepState (default) leaves the game's state in st; ValueOnly (tafl_core.hpp) is for callers that read `r` alone - the playout
+    // kernels hand it in; st is then scratch.  The generic engine always keeps.
+    template <class L = IdxComputed<NL>, class P = KeepState>
+    static TAFL_HD void playout(S& st, uint32_t sk, uint32_t max_plies, const K& C, tafl_rollout_result& r, bool force_generic = false, const L& lut = L(), P pol = P()) {
+        if (fast_ok<NL>(C) && !force_generic) Fast<NL, W>::rollout(st, sk, max_plies, C, r, lut, pol);
         else E::rollout(st, sk, max_plies, C, r);
     }
-    template <class L = IdxComputed<NL>>
+    template <class L = IdxComputed<NL>, class P = KeepState>
     static TAFL_HD void rollout(S st, uint64_t seed, uint64_t game_id, uint32_t sim, uint32_t max_plies, const K& C, tafl_rollout_result& r,
-                                bool force_generic = false, const L& lut = L()) {
-        playout(st, E::sim_key(E::game_key(seed, game_id), sim), max_plies, C, r, force_generic, lut);
+                                bool force_generic = false, const L& lut = L(), P pol = P()) {
+        playout(st, E::sim_key(E::game_key(seed, game_id), sim), max_plies, C, r, force_generic, lut, pol);
     }
     static TAFL_HD void random_advance(S& st, uint64_t seed, uint64_t game_id, uint32_t plies, const K& C, bool force_generic = false) {
         tafl_rollout_result r;
@@ -951,14 +953,14 @@ struct Ops {
     static TAFL_HD uint32_t mcts_scenarios(uint32_t rounds_left, uint32_t planned) { return (rounds_left > 1u && planned < 32u) ? 1u : 2u; }
 
     // playout of slot j of game g (predict() of mcts.py:85 in random-rollout mode), keyed by the leaf's position
-    template <class L = IdxComputed<NL>>
+    template <class L = IdxComputed<NL>, class P = KeepState>
     static TAFL_HD void mcts_slot_rollout(const MctsMem& M, uint32_t j, uint32_t g, uint64_t seed, uint64_t game_id, uint32_t sim_offset,
-                                          uint32_t max_plies, const K& C, const L& lut = L()) {
+                                          uint32_t max_plies, const K& C, const L& lut = L(), P pol = P()) {
         const size_t o = (size_t)j * M.G + g;
         if (j >= M.spec_k || M.spec_kind[o] != 1) return;
         S st; IO::load_rec(M.spec_state + o * IO::QUADS, st);
         tafl_rollout_result r;
-        playout(st, E::sim_key(E::game_key(seed, game_id), sim_offset + M.sim_base[g] + E::state_hash(st, C)), max_plies, C, r, false, lut);
+        playout(st, E::sim_key(E::game_key(seed, game_id), sim_offset + M.sim_base[g] + E::state_hash(st, C)), max_plies, C, r, false, lut, pol);
         M.spec_value[o] = r.value; M.spec_reason[o] = r.reason; M.spec_plies[o] = r.plies; M.spec_kind[o] = 2;
     }
 

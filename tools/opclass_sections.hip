@@ -3,7 +3,8 @@
 // shieldwall filter, repetition tracker), T-layout upkeep, gen (opponent's plays), outcome (filters + outcome_early + apply_finish),
 // each for an attacker's ply (MOVER 0) and a defender's (MOVER 1).
 // Inputs come from memory so that nothing folds away; the load / store instructions at both ends are not part of a ply (they are
-// MEM in the histogram).  Never run: compile with  hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S
+// MEM in the histogram).  -DSEC_VALUE_ONLY: apply_pre and outcome as a value-only playout runs them (tafl_core.hpp: ValueOnly - tracker on
+// packed records in a PlayoutTrack); without it the keeping path.  Never run: compile with  hipcc -O3 --offload-arch=gfx950 --cuda-device-only -S
 #include <hip/hip_runtime.h>
 #include "tafl_fast.hpp"
 using namespace tafl;
@@ -14,7 +15,7 @@ using namespace tafl;
 #endif
 constexpr int NL = SEC_NL, W = SEC_W;
 using E = Engine<NL, W>; using FX = Fast<NL, W>; using S = DState<NL>; using B = Bits<NL>;
-struct Blob { S st; B attT, defT; FX::Gen g; Move m; uint32_t idx, rk; typename E::ApplyCtx ax; typename E::Outcome o; int sw; };
+struct Blob { S st; B attT, defT; FX::Gen g; Move m; uint32_t idx, rk; typename E::ApplyCtx ax; typename E::Outcome o; int sw; PlayoutTrack vt; };
 #define CC preset_consts<NL, W, SEC_PRESET>()
 template <uint32_t MOVER> __device__ __forceinline__ void t_upkeep(Blob& x) {
     const Move m = x.m; const auto& ax = x.ax; B attT = x.attT, defT = x.defT;
@@ -39,13 +40,26 @@ template <uint32_t MOVER> __device__ __forceinline__ void outcome(Blob& x) {
     if constexpr (MOVER == 0) skip_encl = C.rules.enclosure_win == TAFL_ENCL_WITHOUT_EDGE_ACCESS && (x.g.edge_hit || any(x.st.def & C.edge));
     else if (C.rules.exit_fort) skip_fort = !FX::fort_candidate(x.st, x.attT, x.defT, C);
     x.ax.mover = MOVER;
+#ifdef SEC_VALUE_ONLY
+    const typename E::Outcome o = E::template outcome_early<true>(x.st, x.ax, C, skip_encl, skip_fort, x.vt.reached(MOVER, C.rules.n_repetitions));
+#else
     const typename E::Outcome o = E::outcome_early(x.st, x.ax, C, skip_encl, skip_fort);
+#endif
     E::apply_finish(x.st, x.ax, o, o.over ? 1u : x.g.total, C);
+}
+template <uint32_t MOVER> __device__ __forceinline__ void pre(Blob& x) {
+    const auto C = CC;
+#ifdef SEC_VALUE_ONLY
+    E::template apply_pre<IdxComputed<NL>, false>(x.st, x.m, C, x.ax, MOVER);
+    E::template track_value<MOVER>(x.vt, x.m, x.ax.ncap != 0);
+#else
+    E::apply_pre(x.st, x.m, C, x.ax, MOVER);
+#endif
 }
 extern "C" {
 __global__ void sec_pick(Blob* b) { Blob& x = b[threadIdx.x]; const auto C = CC; const uint32_t idx = E::mulhi(E::fmix32(x.rk), x.g.total); x.rk += 0x85EBCA77u; x.m = FX::pick(x.st, x.attT, x.defT, x.g, idx, C); }
-__global__ void sec_apply_pre_att(Blob* b) { Blob& x = b[threadIdx.x]; const auto C = CC; E::apply_pre(x.st, x.m, C, x.ax, 0u); }
-__global__ void sec_apply_pre_def(Blob* b) { Blob& x = b[threadIdx.x]; const auto C = CC; E::apply_pre(x.st, x.m, C, x.ax, 1u); }
+__global__ void sec_apply_pre_att(Blob* b) { pre<0>(b[threadIdx.x]); }
+__global__ void sec_apply_pre_def(Blob* b) { pre<1>(b[threadIdx.x]); }
 __global__ void sec_gen_att(Blob* b) { Blob& x = b[threadIdx.x]; const auto C = CC; const auto fc = make_fast_consts<NL>(C); FX::gen(x.st, x.attT, x.defT, 0u, C, fc, x.g); }
 __global__ void sec_gen_def(Blob* b) { Blob& x = b[threadIdx.x]; const auto C = CC; const auto fc = make_fast_consts<NL>(C); FX::gen(x.st, x.attT, x.defT, 1u, C, fc, x.g); }
 __global__ void sec_outcome_att(Blob* b) { outcome<0>(b[threadIdx.x]); }

@@ -8,7 +8,8 @@
 //         -mllvm --amdgpu-sched-strategy=max-ilp -o /tmp/rollout_bench tools/rollout_bench.hip
 //   /tmp/rollout_bench [board: 11|13|7] [max_plies=512] [reps=3]
 // -DLUT: bit_at from the LDS table of tafl_tables.hpp (boards 11 and 7), as in the product's preset playout kernels; without it the
-// computed code.  -DDENSE13: board 13 in the dense 13-column layout <6, 13> the product's 13x13 playout kernels work in.
+// computed code.  -DTAFL_PLAYOUT_KEEP: the keeping playout (what random_advance runs) instead of the value-only one of the playout kernels
+// (tafl_core.hpp).  -DDENSE13: board 13 in the dense 13-column layout <6, 13> the product's 13x13 playout kernels work in.
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(64, LB) void k_roll(const Quad* soa, uint32_t n, ui
     if constexpr (NLS == NL && WS == W) StateIO<NL>::load_soa(soa, n, g, st);
     else { DState<NLS> t; StateIO<NLS>::load_soa(soa, n, g, t); restride<NLS, WS, NL, W>(t, C.n, st); }
     tafl_rollout_result r;
-    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut);
+    Ops<NL, W>::rollout(st, seed, base + g, sim, max_plies, C, r, false, lut, KernelPlayout());
     out[g] = r;
 }
 template <int NL>
