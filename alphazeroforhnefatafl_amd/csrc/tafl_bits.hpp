@@ -45,6 +45,17 @@ extern "C" unsigned long long tafl_stat_acc[32];
 #define TAFL_STAT_HIT(k) ((void)0)
 #endif
 
+// filter probes for host-side test builds only (-DTAFL_FILTER_PROBE, tests/hostsim_filters): a pre-filtered block runs whatever its filter
+// says and reports (rule, what the filter said, what the block found); the harness checks that the filter never says no to a yes
+#if defined(TAFL_FILTER_PROBE) && !defined(__HIP_DEVICE_COMPILE__)
+extern "C" void tafl_filter_probe(int rule, bool filter, bool full);
+#define TAFL_FILTER_OPEN(p) true
+#define TAFL_FILTER_SEEN(rule, filter, full) tafl_filter_probe((rule), (filter), (full))
+#else
+#define TAFL_FILTER_OPEN(p) (p)
+#define TAFL_FILTER_SEEN(rule, filter, full) ((void)0)
+#endif
+
 namespace tafl {
 
 // true if the predicate holds for ANY game of the wavefront (device) / for this game (host build): used to skip work that

@@ -238,7 +238,35 @@ struct Fast {
         const bool ok_hi = (first_above & (ld >> (pos + 1u))) != 0u;                 // ... exists and is a defender
         const uint32_t hb = 31u - (uint32_t)__builtin_clz(below | 1u);                // nearest occupied tile on the low side (below != 0)
         const bool ok_lo = below != 0u && ((ld >> hb) & 1u) != 0u;
-        return (top || bot || lef || rig) && kr < n && kc < n && ok_hi && ok_lo;
+        const bool on_edge = (top || bot || lef || rig) && kr < n && kc < n;
+        if (on_edge) TAFL_STAT_HIT(16);
+        bool cand = on_edge && ok_hi && ok_lo;
+        if (cand) TAFL_STAT_HIT(15);
+        // Second stage, entered by a wave only when some game passed the flank test.  Positions are those of the king's edge line E; I is
+        // the line next to it (row / column 1 or n-2), J the one behind I.  With both flanks defenders, the RUN - the tiles of E strictly
+        // between them - consists of the king's tile and empty tiles connected to it along E, so every tile of the run is in the flooded
+        // region (above).  The flood returns None as soon as an attacker stands next to a region tile (logic.rs:288-291), and an empty tile
+        // next to a region tile is a region tile.  Hence each of these makes the flood None, and its absence is necessary for a fort:
+        //   T1  an attacker on I opposite a tile of the run                        (next to a run tile);
+        //       region tiles of I: reg = the empty tiles of I opposite the run, and the empty tiles of I beside one of those;
+        //   T2  an attacker on I beside a tile of the first kind                   (next to a region tile of I);
+        //   T3  an attacker on J opposite a tile of reg                            (next to a region tile of I).
+        // (reg holds no corner: a corner lies on E.)  For n = 3, 4 the lines coincide in part; every statement above is about tiles at
+        // distance one of each other and stays true.
+        if (wave_any(cand)) {
+            const uint32_t i1 = (uint32_t)W, i2 = lb - (uint32_t)W, j1 = 2u * (uint32_t)W, j2 = lb - 2u * (uint32_t)W;
+            const uint32_t ia = top ? line_bits(st.att, i1, n) : bot ? line_bits(st.att, i2, n) : lef ? line_bits(attT, i1, n) : line_bits(attT, i2, n);
+            const uint32_t id = top ? line_bits(st.def, i1, n) : bot ? line_bits(st.def, i2, n) : lef ? line_bits(defT, i1, n) : line_bits(defT, i2, n);
+            const uint32_t ja = top ? line_bits(st.att, j1, n) : bot ? line_bits(st.att, j2, n) : lef ? line_bits(attT, j1, n) : line_bits(attT, j2, n);
+            // the run: below the high flank (first_above, moved back to its place on the line), above the low flank (bit hb)
+            const uint32_t run = ((first_above << (pos + 1u)) - 1u) & ~((2u << hb) - 1u);
+            const uint32_t open = ~(ia | id) & ((1u << n) - 1u);
+            const uint32_t r1 = run & open;
+            const uint32_t beside = (r1 << 1) | (r1 >> 1);
+            const uint32_t reg = r1 | (beside & open);
+            cand = cand && ((ia & (run | beside)) | (ja & reg)) == 0u;
+        }
+        return cand;
     }
 
     // ---- one ply of a playout with the mover known at compile time -----------------------------------------------------------------------

@@ -4,6 +4,7 @@ event counters (-DTAFL_STAT), 3 000 random playouts from the start position.  CP
 
   g++ -O2 -std=c++17 -fPIC -ffp-contract=off -DTAFL_STAT -shared -o /tmp/libhostsim_stat.so tests/hostsim/hostsim.cpp -lm
   python tools/playout_event_stats.py [c11|b7]
+(or, a build of a minute: make -C tests/hostsim_filters libhostsim_filters_stat.so, and TAFL_HOSTSIM_STAT_LIB=tests/hostsim_filters/libhostsim_filters_stat.so)
 P(wave of 64) = 1 - (1 - p)^64: the share of wave-plies in which at least one of 64 games takes the path."""
 import ctypes as C, sys
 ROOT = __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__)))
@@ -26,8 +27,9 @@ L.hs_rollout.argtypes = [C.POINTER(TaflRules), C.c_uint8, C.c_uint32, C.POINTER(
 assert L.hs_rollout(C.byref(r), n, wb, states, G, 2, 0, 512, 0, out) == 0
 N = acc[31]
 names = {0: 'exit_fort entered (defender moved)', 1: 'king on edge', 2: 'ring1: no attacker next to king', 3: 'ring1 empty nb, no corner', 4: 'ring2 passed -> flood', 5: 'flood ok -> secure',
-         13: 'fort candidate (edge-line flank test)', 8: 'shieldwall filter passed', 9: 'king adjacent', 10: 'enclosure flood entered', 11: 'ply with captures', 12: 'non-custodial captures'}
+         16: 'king on an edge line (defender moved)', 15: 'fort: flank test passed (stage 1)', 13: 'fort candidate (flank + inner lines)', 8: 'shieldwall filter passed',
+         9: 'king adjacent', 14: 'king adjacent and far can count', 10: 'enclosure flood entered', 11: 'ply with captures', 12: 'non-custodial captures'}
 print(board, 'plies', N)
 for k, nm in names.items():
     p = acc[k] / N
-    print('  %-38s %9d  %.4f %% per ply   P(wave of 64) = %.3f' % (nm, acc[k], 100 * p, 1 - (1 - p) ** 64))
+    print('  %-40s %9d  %.4f %% per ply   P(wave of 64) = %.3f' % (nm, acc[k], 100 * p, 1 - (1 - p) ** 64))
