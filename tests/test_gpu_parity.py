@@ -15,27 +15,12 @@ from alphazeroforhnefatafl_amd import abi
 from alphazeroforhnefatafl_amd.abi import TaflMctsParams, TaflPlay, TaflState
 from oracle import oracle as orc
 from tests import parity_util as pu
+from tests.board_sizes_util import expand_compare_gpu as _expand_compare_gpu, gpu_batch, gpu_logic    # (shared with tests/test_gpu_board_sizes.py)
 from tests.kat_util import KATS, REASON_CODE, play, ruleset, side_of, status_tuple, tiles
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-_LOGICS = {}
-
-
-def gpu_logic(rules, n, wb):
-    from alphazeroforhnefatafl_amd.engine import BatchedGameLogic
-    key = (bytes(rules.to_c()), n, wb)
-    if key not in _LOGICS:
-        _LOGICS[key] = BatchedGameLogic(rules, n, wb)
-    return _LOGICS[key]
-
-
-def gpu_batch(rules, n, wb, states, G):
-    lg = gpu_logic(rules, n, wb)
-    b = lg.new_batch(G)
-    b.upload(states)
-    return b
 
 
 def _mk(name):
@@ -124,33 +109,6 @@ def test_lockstep_games(name):
         if t % 10 == 9 or t == T - 1:
             got = b.download()
             assert pu.states_equal(states, got, G), (name, t, pu.first_state_diff(states, got, G))
-
-
-def _expand_compare_gpu(rules, n, wb, lst, tag):
-    lg = orc.GameLogic(rules, n)
-    G = len(lst)
-    states = pu.states_array(lst)
-    b = gpu_batch(rules, n, wb, states, G)
-    oc, om = orc.batch_movegen(lg, states, G, wb)
-    gc, gm = b.iter_plays()
-    assert list(oc) == list(gc), tag
-    assert bytes(om) == bytes(gm), tag
-    arr, ranks, total, src = pu.expand_all(states, G, oc)
-    cov = collections.Counter()
-    if total == 0:
-        return cov
-    a = pu.clone_states(arr, total)
-    op, oe = orc.batch_step_kth(lg, a, total, wb, ranks)
-    b2 = gpu_batch(rules, n, wb, arr, total)
-    gp, ge = b2.do_kth_play(ranks)
-    got = b2.download()
-    for i in range(total):
-        assert pu.play_tuple4(op[i]) == pu.play_tuple4(gp[i]), (tag, i)
-        assert pu.effects_tuple(oe[i]) == pu.effects_tuple(ge[i]), (tag, i, pu.describe_state(arr[i], wb), pu.play_tuple4(op[i]))
-        cov[(oe[i].status, oe[i].reason)] += 1
-    assert pu.states_equal(a, got, total), (tag, pu.first_state_diff(a, got, total))
-    b.close(); b2.close()
-    return cov
 
 
 def test_rare_rules_crafted_positions():
