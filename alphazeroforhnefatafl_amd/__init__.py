@@ -7,7 +7,7 @@ from . import abi
 from .abi import Ruleset, boards, rules
 
 __all__ = ["abi", "Ruleset", "boards", "rules", "BatchedGameLogic", "GameBatch", "MCTS", "MCTSArgs", "GuidedMCTS", "BatchedGame", "Examples", "Pool",
-           "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult", "playout_cap_is_full"]
+           "play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult", "playout_cap_is_full", "apply_eval_symmetry"]
 
 
 def __getattr__(name):
@@ -15,7 +15,7 @@ def __getattr__(name):
     if name in ("BatchedGameLogic", "GameBatch", "Examples", "Pool"):
         from . import engine
         return getattr(engine, name)
-    if name in ("MCTS", "MCTSArgs", "GuidedMCTS", "playout_cap_is_full"):
+    if name in ("MCTS", "MCTSArgs", "GuidedMCTS", "playout_cap_is_full", "apply_eval_symmetry"):
         from . import mcts
         return getattr(mcts, name)
     if name in ("play_episodes", "play_guided_episodes", "play_guided_selfplay", "play_match", "MatchResult"):

@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -90,6 +90,8 @@ SYMBOLS = [
     ("tafl_gmatch_step", _i32, [_vp, _P(_vp), _P(_vp), _i32]),
     ("tafl_gmatch_get_stats", _i32, [_vp, _P(TaflMatchStats)]),
     ("tafl_gmcts_set_root_noise", _i32, [_vp, _P(TaflRootNoise)]),
+    ("tafl_gmcts_set_eval_symmetry", _i32, [_vp, _P(TaflEvalSymmetry)]),
+    ("tafl_gmcts_leaf_symmetry", _i32, [_vp, _vp, _i32]),
     ("tafl_gselfplay_set_playout_cap", _i32, [_vp, _P(TaflPlayoutCap)]),
     ("tafl_gselfplay_playout_cap_stats", _i32, [_vp, _P(TaflPlayoutCapStats)]),
     ("tafl_gselfplay_set_forced_playouts", _i32, [_vp, _P(TaflForcedPlayouts)]),

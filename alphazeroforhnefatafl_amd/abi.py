@@ -195,6 +195,11 @@ class TaflSolverStats(C.Structure):
                 ("pruned_visits", C.c_uint64), ("pruned_children", C.c_uint64), ("moves", C.c_uint64)]
 
 
+class TaflEvalSymmetry(C.Structure):
+    """tafl_eval_symmetry: a random board symmetry per leaf evaluation of a guided search or run (tafl_gmcts_set_eval_symmetry)."""
+    _fields_ = [("seed", C.c_uint64), ("game_id_base", C.c_uint64), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
+
+
 class TaflEpisodeOpts(C.Structure):
     """tafl_episode_opts: a guided self-play run in episodes (tafl_gselfplay_begin_episodes)."""
     _fields_ = [("id_stride", C.c_uint64), ("episode_moves", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 4)]
@@ -245,6 +250,7 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_root_noise": 48, "tafl_episode_opts": 32, "tafl_episode_stats": 64, "tafl_match_opts": 32, "tafl_match_io": 72,
                   "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
                   "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
+                  "tafl_eval_symmetry": 32,
                   "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
@@ -255,7 +261,7 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_episode_stats", TaflEpisodeStats), ("tafl_match_opts", TaflMatchOpts), ("tafl_match_io", TaflMatchIo),
                     ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats),
                     ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats),
-                    ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats),
+                    ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats), ("tafl_eval_symmetry", TaflEvalSymmetry),
                     ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 

@@ -807,13 +807,15 @@ struct Engine {
             return hash_rows<R + 1>(st, n, h);
         } else return h;
     }
-    static TAFL_HD uint32_t state_hash(const S& st, const K& C) {
-        uint32_t h = hash_rows<0>(st, C.n, C.n);
+    static TAFL_HD uint32_t state_hash(const S& st, const K& C) { return state_hash(st, C.n); }
+    // (the board's side length is all the key takes from the constants)
+    static TAFL_HD uint32_t state_hash(const S& st, uint32_t n) {
+        uint32_t h = hash_rows<0>(st, n, n);
         TAFL_UNROLL for (int i = 0; i < 4; ++i) h = mm3_word(h, st.rep[i]);
         h = mm3_word(h, st.turn);
         h = mm3_word(h, st.reps);
         h = mm3_word(h, st.flags & 0x00FF0007u);
-        h ^= (C.n + 7u) * 4u;
+        h ^= (n + 7u) * 4u;
         return fmix32(h);
     }
     static TAFL_HD uint32_t ply_rand(uint32_t sk, uint32_t ply) { return fmix32(sk + ply * 0x85EBCA77u); }

@@ -121,6 +121,18 @@ static TAFL_HD uint32_t sym_action(uint32_t sym, uint32_t a, uint32_t n) {
     return tiles_action(sym_tile(sym, from, n), sym_tile(sym, to, n), n);
 }
 
+// the same for a move that is at hand as (row, column, direction, distance) of its from tile (directions: 0 r+, 1 r-, 2 c+, 3 c-, the
+// order of the slots): the tile is transformed once, the direction by what each step of the symmetry does to it - the transposition
+// swaps vertical and horizontal, a mirror reverses the directions along its axis - and the distance stays.  No division.
+static TAFL_HD uint32_t sym_move_action(uint32_t sym, uint32_t r, uint32_t c, uint32_t dir, uint32_t dist, uint32_t n) {
+    if (sym & 4u) { const uint32_t x = r; r = c; c = x; dir ^= 2u; }
+    if (sym & 1u) { r = n - 1u - r; if (dir < 2u) dir ^= 1u; }
+    if (sym & 2u) { c = n - 1u - c; if (dir >= 2u) dir ^= 1u; }
+    const uint32_t nm = n - 1u;
+    const uint32_t slot = dir == 0u ? dist - 1u : dir == 1u ? (nm - r) + dist - 1u : dir == 2u ? nm + dist - 1u : nm + (nm - c) + dist - 1u;
+    return (r * n + c) * 2u * nm + slot;
+}
+
 // z of an example whose side to move was `side` (TAFL_ATTACKER / TAFL_DEFENDER), from the game's current flags word: +1 that side won,
 // -1 it lost, TAFL_DRAW_VALUE (1e-4) a draw; fin = 0 and z = 0 while the game is going on
 static TAFL_HD float example_outcome(uint32_t flags, uint32_t side, uint8_t& fin) {

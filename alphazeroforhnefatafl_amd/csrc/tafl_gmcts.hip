@@ -1,16 +1,6 @@
 // tafl_gmcts.hip — guided MCTS: the search whose leaves an external evaluator scores (tafl_guided.hpp), kernels and tafl_gmcts_* entry points.
 #include "tafl_internal.hpp"
 
-enum { GS_SIMS = 0, GS_PREDICTS, GS_TERMINAL, GS_FAULTS, GS_DEPTH, GS_WAITING, GS_COUNT };
-// what one lane's round adds to the counters of a step kernel
-static __device__ __forceinline__ void gstats_flush(const GuidedStats& gs, bool waiting, unsigned long long* stats) {
-    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
-    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
-    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
-    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
-    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
-    if (waiting) atomicAdd(&stats[GS_WAITING], 1ull);
-}
 
 template <int NL, int W>
 __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_init(Consts<NL> C, const Quad* soa, GuidedMem M) {
@@ -67,8 +57,23 @@ __global__ __launch_bounds__(256) void k_gmcts_leaves(Consts<NL> C, GuidedMem M,
     const uint32_t L = wait ? M.leaf[g] : 0u;
     const uint32_t* rec = (const uint32_t*)(M.node_state + ((size_t)L * M.G + g) * StateIO<NL>::QUADS);   // att[NL], def[NL], rep[4], meta[4]
     const uint32_t aw = rec[bit >> 5], dw = rec[NL + (bit >> 5)], flags = rec[2 * NL + 7];
-    boards[i] = (uint8_t)board_value((aw >> (bit & 31)) & 1u, (dw >> (bit & 31)) & 1u, r, c, C.n, flags);
+    // a waiting leaf is shown under its symmetry (tafl_eval_symmetry): the byte of tile t goes to tile sym_tile(s, t) of the game's row
+    size_t o = i;
+    if (M.sym && wait) {
+        const uint32_t s = M.sym[g];
+        uint32_t r2 = (s & 4u) ? c : r, c2 = (s & 4u) ? r : c;
+        if (s & 1u) r2 = C.n - 1u - r2;
+        if (s & 2u) c2 = C.n - 1u - c2;
+        o = (size_t)g * nn + r2 * C.n + c2;
+    }
+    boards[o] = (uint8_t)board_value((aw >> (bit & 31)) & 1u, (dw >> (bit & 31)) & 1u, r, c, C.n, flags);
     if (t == 0) { sides[g] = (uint8_t)((flags & TAFL_F_SIDE) ? TAFL_DEFENDER : TAFL_ATTACKER); waiting[g] = wait ? 1 : 0; }
+}
+// the symmetry every waiting leaf is shown under (tafl_gmcts_leaf_symmetry): 0 for a game that does not wait, and with the setting off
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_leaf_symmetry(GuidedMem M, uint8_t* out) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    out[g] = (M.sym && M.kind[g] == 1) ? M.sym[g] : (uint8_t)0;
 }
 template <int NL, int W>
 __global__ __launch_bounds__(TAFL_BLOCK) void k_gmcts_root_children(Consts<NL> C, GuidedMem M, tafl_root_child* out, uint32_t max_children, uint32_t* out_n) {
@@ -401,6 +406,18 @@ static RootNoise noise_arg(const tafl_root_noise& cfg) {
     return nz;
 }
 
+// a begin latches the batch's eval-symmetry setting into the arena's argument struct (after gmcts_arena has bound the rest): off, or one
+// byte per game, the seed and the game id base of the search (cfg's) or run (its own)
+static int evalsym_latch(tafl_batch* b, uint64_t game_id_base) {
+    tafl_ctx* c = b->ctx; GuidedMem& M = b->gmem;
+    M.sym = nullptr; M.sym_seed = 0; M.sym_gid = 0; M.sym_n = 0;
+    if (!b->evalsym_set) return TAFL_OK;
+    NEED(b->g_sym, b->n);
+    HIPCHK(hipMemsetAsync(b->g_sym.p, 0, b->n, c->stream));
+    b->g_sym.bind(M.sym); M.sym_seed = b->evalsym_cfg.seed; M.sym_gid = game_id_base; M.sym_n = c->n;
+    return TAFL_OK;
+}
+
 // a tafl_playout_cap the library accepts
 static int cap_check(const tafl_playout_cap* cfg) {
     if (cfg->fast_sims < 2u || cfg->fast_sims > 0xFFFFu || cfg->full_per_65536 > 65536u)
@@ -482,6 +499,27 @@ int tafl_gselfplay_playout_cap_stats(tafl_batch* b, tafl_playout_cap_stats* out)
     return TAFL_OK;
 }
 
+int tafl_gmcts_set_eval_symmetry(tafl_batch* b, const tafl_eval_symmetry* cfg) {
+    if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_set_eval_symmetry: null batch");
+    if (!cfg) { b->evalsym_set = false; return TAFL_OK; }
+    if (cfg->flags != 0 || cfg->_reserved[0] != 0 || cfg->_reserved[1] != 0 || cfg->_reserved[2] != 0)
+        return fail(TAFL_ERR_UNSUPPORTED, "tafl_eval_symmetry: flags and reserved words must be 0");
+    b->evalsym_set = true; b->evalsym_cfg = *cfg;
+    return TAFL_OK;
+}
+
+int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device) {
+    if (!b || !b->g_has || !out_sym) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_leaf_symmetry: bad argument");
+    tafl_ctx* c = b->ctx; const uint32_t n = b->n;
+    HIPCHK(hipSetDevice(c->device));
+    uint8_t* d;
+    STAGED(d, b->g_wait, out_sym, n, out_is_device);
+    LAUNCH_PER_GAME(k_gmcts_leaf_symmetry, c, n, b->gmem, d);
+    HIPCHK(hipGetLastError());
+    if (!out_is_device) COPY_OUT(out_sym, d, n, c->stream);
+    return sync_ok(c);
+}
+
 int tafl_gmcts_set_root_noise(tafl_batch* b, const tafl_root_noise* cfg) {
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_set_root_noise: null batch");
     if (!cfg) { b->noise_set = false; return TAFL_OK; }
@@ -551,6 +589,7 @@ int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_nod
     if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     HIPCHK(hipSetDevice(c->device));
     if (flags & TAFL_GMCTS_KEEP_TREE) { if (const int rc = join_search(b)) return rc; }
+    if (const int rc = evalsym_latch(b, b->evalsym_cfg.game_id_base)) return rc;      // and the eval symmetry (a retained tree: its new leaves)
     if ((flags & TAFL_GMCTS_KEEP_TREE) && b->g_has && b->g_tree_live) {
         b->g_tree_live = false;
         const int rc = gmcts_begin_keep(b, max_sims, edges_per_node);
@@ -575,7 +614,8 @@ int tafl_gmcts_step(tafl_batch* b, const float* priors, const float* values, int
     if (const int rc = stage_evaluation(b, priors, values, in_is_device)) return rc;
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
-    if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st, b->g_noise); });
+    if (b->gmem.sym) { if (const int rc = gsym_launch_step(b, priors, values, A, c_puct, n_sims, st)) return rc; }      // the search latched the eval symmetry
+    else if (b->g_noise_on) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W, true>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st, b->g_noise); });
     else dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gmcts_step<t.NL, t.W>), c, n, t.CC, b->gmem, priors, values, A, c_puct, n_sims, st); });
     HIPCHK(hipGetLastError());
     return gmcts_waiting(b, out_waiting);
@@ -685,6 +725,7 @@ static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
+    if (b->gmem.sym) return gsym_launch_selfplay(b, dp, dv, A, st);      // the run latched the eval symmetry: rounds (and reopen) of their own
     if (b->gsp_solver_on) {                                     // exact proofs: rounds of their own (whatever the noise, the cap and the forcing), then the reopen
         const bool nz = b->g_noise_on, ep = b->gsp_episodes;
 #define TAFL_SOLVER(NZ, EP) dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_solver<t.NL, t.W, NZ, EP>), c, n, t.CC, b->gmem, b->soa, dp, dv, A, b->gsp_cpuct, b->gsp_sims, b->gsp, b->gsp_ep, b->gsp_rec, st, b->g_noise, b->gsp_cap, b->gsp_forced, b->gsp_solver); })
@@ -759,6 +800,7 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     HIPCHK(hipSetDevice(c->device));
     b->tree_live = false; b->g_tree_live = false; b->ran = false;      // the run plays away from the roots of both retained trees
     if (const int rc = gmcts_arena(b, n_sims, edges_per_node, "tafl_gselfplay_begin")) return rc;
+    if (const int rc = evalsym_latch(b, game_id_base)) return rc;      // the run latches the eval symmetry; its game ids are the run's own
     NEED(b->gsp_moves_done, sizeof(uint32_t) * (size_t)n); NEED(b->gsp_plays, sizeof(tafl_play) * (size_t)n * n_moves);
     b->gsp_moves_done.bind(b->gsp.moves_done); b->gsp_plays.bind(b->gsp.plays); b->gsp.n_moves = n_moves;
     b->gsp_episodes = eo != nullptr; b->gsp_ep = GEpisodes{};
@@ -870,6 +912,7 @@ int tafl_gmatch_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_node, d
     if (b->cap_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: a playout cap is set on the batch (tafl_gselfplay_set_playout_cap(NULL) first)");
     if (b->solver_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: the solver is set on the batch (tafl_gselfplay_set_solver(NULL) first)");
     if (b->forced_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: forced playouts are set on the batch (tafl_gselfplay_set_forced_playouts(NULL) first)");
+    if (b->evalsym_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmatch_begin: the eval symmetry is set on the batch (tafl_gmcts_set_eval_symmetry(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     if (const int rc = gselfplay_begin(b, n_sims, edges_per_node, c_puct, o, n_moves, game_id_base, ex, eo, openings ? openings : b)) return rc;
     b->gsp_active = false; b->gsp_has = false;                 // (the run counts as open once its match buffers exist)

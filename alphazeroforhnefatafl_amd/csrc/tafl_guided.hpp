@@ -22,6 +22,10 @@
 // A guided self-play run records its examples and draws its plays with the functions of tafl_examples.hpp (example_append,
 // visit_draw, which own the example layout and the board encoding); this file only walks the root's edge block for them.
 //
+// Evaluation under a random board symmetry (include/taflhip.h tafl_eval_symmetry) is compiled only into the SYM
+// instantiations (the kernels of tafl_gmcts_sym.hip): where a leaf starts to wait its symmetry is drawn into GuidedMem::sym, and
+// expand_as reads the prior of a legal move at the permuted index.  The functions without the flag are what they were.
+//
 // Exact win/loss proofs (MCTS-Solver: include/taflhip.h tafl_solver) are compiled only into the SOLVER
 // instantiations (selfplay_step_solver).  A node's proof lives in bits 1-2 of GNode::expanded (a terminal's is its term code), the
 // losing-move / winning-move mark of an edge in bits 2-3 of GEdge::dir, mirrored there through pedge when the child is proven, so the
@@ -57,6 +61,11 @@ struct GuidedMem {
     uint8_t* fault;              // [G] arena overflow / no selectable action: the game stops searching
     uint32_t* sims_done;         // [G]
     uint32_t G, node_cap, edge_cap;
+    // evaluation under a random board symmetry (include/taflhip.h tafl_eval_symmetry): read by the SYM
+    // instantiations of the rounds alone, which run only when sym != nullptr; the leaves kernel and the getter test the pointer
+    uint8_t* sym = nullptr;      // [G] the symmetry the leaf that waits is shown under: written where kind[g] becomes 1
+    uint64_t sym_seed = 0, sym_gid = 0;   // the game id of game g is sym_gid + g
+    uint32_t sym_n = 0;          // the board's side length (the close-and-reopen kernel has no Consts)
 };
 struct GuidedStats { uint32_t sims, predicts, terminal_hits, faults, depth; };
 // per-run state of a guided self-play run (tafl_gselfplay_*)
@@ -119,6 +128,12 @@ struct RootNoise {
     uint64_t seed, gid;          // gid = game_id_base + g
     uint32_t move_no;            // M
 };
+// the symmetry a leaf with the leaf key `h` (Engine::state_hash) is shown under in game gid: a pure function of (seed, gid, position)
+constexpr uint64_t kSymKey = 0x53594D4D45545259ull;
+static TAFL_HD uint32_t eval_symmetry_of(uint64_t seed, uint64_t gid, uint32_t h) {
+    using E = Engine<2, 7>;
+    return E::ply_rand(E::sim_key(E::game_key(seed, gid) ^ kSymKey, h), 0u) >> 29;
+}
 constexpr uint32_t kNoiseTries = 16;         // rejection rounds of one Gamma variate before its fallback
 constexpr uint32_t kNoiseWordsPerTry = 5;    // uniform words one round consumes; the words of the boost follow at kNoiseTries * kNoiseWordsPerTry
 
@@ -174,6 +189,11 @@ struct Guided {
         M.hdr[g] = h; M.pedge[g] = 0;
         IO::store_rec(M.node_state + (size_t)g * IO::QUADS, root);
         M.node_top[g] = 1; M.edge_top[g] = 0; M.leaf[g] = 0; M.kind[g] = 0; M.fault[g] = 0; M.sims_done[g] = 0;
+    }
+
+    // SYM: the leaf `st` of game g starts to wait (kind[g] has just become 1): draw its symmetry
+    static TAFL_HD void leaf_symmetry(const GuidedMem& M, uint32_t g, const S& st) {
+        M.sym[g] = (uint8_t)eval_symmetry_of(M.sym_seed, M.sym_gid + g, E::state_hash(st, M.sym_n));
     }
 
     // np.sum over the dense action vector whose only non-zero entries are e[0..cnt) (ascending action index); `add1`
@@ -274,19 +294,25 @@ struct Guided {
     static TAFL_HD bool expand(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C) { return expand_as<false>(M, g, priors, A, C, nullptr); }
     // NOISE: when the leaf is node 0, P' = (1 - epsilon) P + epsilon eta (tafl_root_noise): the raw variates wait in the fresh edges' q
     // between the two passes (mix == false: this search takes no noise - a fast move of a capped run)
-    template <bool NOISE>
+    // SYM (the rounds of a search or run that latched tafl_eval_symmetry): the evaluator saw this leaf under symmetry s = sym[g], so the
+    // prior of action a stands at sym_action(s, a) of its answer; the move is at hand as (from, dir, dist), which sym_move_action takes
+    template <bool NOISE, bool SYM = false>
     static TAFL_HD bool expand_as(const GuidedMem& M, uint32_t g, const float* priors, uint32_t A, const K& C, const RootNoise* nz, bool mix = true) {
         const uint32_t L = M.leaf[g];
         S st; IO::load_rec(M.node_state + ((size_t)L * M.G + g) * IO::QUADS, st);
         const uint32_t base = M.edge_top[g];
         GEdge* e = &M.edges[(size_t)g * M.edge_cap + base];
         const uint32_t side = st.flags & TAFL_F_SIDE;
+        [[maybe_unused]] uint32_t s = 0;
+        if constexpr (SYM) s = M.sym[g];
         Move cur = E::canon_start();
         uint32_t cnt = 0;
         while (E::canon_next(st, side, C, cur)) {                 // getValidMoves, canonical = ascending action index
             if (base + cnt >= M.edge_cap) return false;
             const uint32_t a = O::action_of(cur, C);
-            GEdge ne; ne.p = (double)priors[a] * 1.0; ne.q = 0.0; ne.n = 0; ne.child = 0; ne.action = a;
+            uint32_t pa = a;
+            if constexpr (SYM) pa = sym_move_action(s, cur.from / (uint32_t)W, cur.from % (uint32_t)W, cur.dir, cur.dist, C.n);
+            GEdge ne; ne.p = (double)priors[pa] * 1.0; ne.q = 0.0; ne.n = 0; ne.child = 0; ne.action = a;
             ne.from = (uint16_t)cur.from; ne.dir = (uint8_t)cur.dir; ne.dist = (uint8_t)cur.dist;
             e[cnt++] = ne;
         }
@@ -321,14 +347,15 @@ struct Guided {
     // SOLVER (the solver rounds, include/taflhip.h tafl_solver rules 1-5): terminals prove their parents, backup_solver carries the
     // proofs up, the scan of a node skips its losing moves, and a proven root ends the search; sl[SL_COUNT] counts for this lane.  The
     // forced-playouts argument is a run-time one there: k == 0 forces nothing
-    template <bool NOISE, bool FORCED = false, bool SOLVER = false>
+    // SYM: leaves are expanded through the permuted index (expand_as) and a leaf that starts to wait draws its symmetry
+    template <bool NOISE, bool FORCED = false, bool SOLVER = false, bool SYM = false>
     static TAFL_HD void step_as(const GuidedMem& M, uint32_t g, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                 const K& C, GuidedStats& gs, const RootNoise* nz, bool mix = true, const ForcedPlayouts* fp = nullptr, uint32_t* forced = nullptr,
                                 uint32_t* sl = nullptr) {
         if (M.fault[g]) { M.kind[g] = 3; return; }
         uint32_t sims = M.sims_done[g];
         if (M.kind[g] == 1) {
-            if (!priors || !expand_as<NOISE>(M, g, priors, A, C, nz, mix)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
+            if (!priors || !expand_as<NOISE, SYM>(M, g, priors, A, C, nz, mix)) { M.fault[g] = 1; gs.faults += 1; M.kind[g] = 3; return; }
             gs.predicts += 1;
             if constexpr (SOLVER) backup_solver(M, g, M.leaf[g], -(double)value, PROOF_NONE, sl);
             else backup(M, g, M.leaf[g], -(double)value);         // return -v (mcts.py:102) into the callers
@@ -345,7 +372,11 @@ struct Guided {
                     else backup(M, g, cur, -O::term_value(h.term));
                     gs.terminal_hits += 1; break;
                 }
-                if (!(SOLVER ? h.expanded & 1 : h.expanded)) { M.leaf[g] = cur; M.kind[g] = 1; waiting = true; break; }   // mcts.py:83-85
+                if (!(SOLVER ? h.expanded & 1 : h.expanded)) {                                                // mcts.py:83-85
+                    M.leaf[g] = cur; M.kind[g] = 1; waiting = true;
+                    if constexpr (SYM) { S ls; IO::load_rec(M.node_state + ((size_t)cur * M.G + g) * IO::QUADS, ls); leaf_symmetry(M, g, ls); }
+                    break;
+                }
                 gs.depth += 1;
                 GEdge* eb = &M.edges[(size_t)g * M.edge_cap + h.edge_base];
                 const double sq = sqrt((double)h.ns), sq0 = sqrt((double)h.ns + TAFL_MCTS_EPS);
@@ -585,7 +616,8 @@ struct Guided {
     // SOLVER: the round of a run with exact proofs (include/taflhip.h tafl_solver).  Every search, full or fast, proves what it can
     // (step_as); when it is complete solver_prune edits the root's visit counts in place, before forced_prune, and the rest reads n'.
     // Forced playouts are a run-time matter there (fp->k == 0: none)
-    template <bool NOISE, bool EPISODES, bool CAP = false, bool FORCED = false, bool SOLVER = false>
+    // SYM: every search of the run shows its leaves under their symmetries (step_as)
+    template <bool NOISE, bool EPISODES, bool CAP = false, bool FORCED = false, bool SOLVER = false, bool SYM = false>
     static TAFL_HD void selfplay_step_as(const GuidedMem& M, uint32_t g, Quad* soa, const float* priors, float value, uint32_t A, double c_puct, uint32_t n_sims,
                                          const GSelfPlay& sp, const SelfPlayRec& rec, const K& C, GuidedStats& gs, const RootNoise* nz, const GEpisodes* ep,
                                          const PlayoutCap* pc = nullptr, const ForcedPlayouts* fp = nullptr, const SolverCfg* sv = nullptr) {
@@ -611,16 +643,16 @@ struct Guided {
         for (;;) {
             if constexpr (SOLVER) {
                 uint32_t forced = 0, sl[SL_COUNT] = {0u, 0u, 0u};
-                step_as<NOISE, true, true>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced, sl);
+                step_as<NOISE, true, true, SYM>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced, sl);
                 if (forced) TAFL_COUNT_ADD(&fp->counters[FP_FORCED_SIMS], forced);
                 if (sl[SL_SKIPPED]) TAFL_COUNT_ADD(&sv->counters[SV_SKIPPED_SIMS], sl[SL_SKIPPED]);
                 if (sl[SL_NODES_WON]) TAFL_COUNT_ADD(&sv->counters[SV_NODES_WON], sl[SL_NODES_WON]);
                 if (sl[SL_NODES_LOST]) TAFL_COUNT_ADD(&sv->counters[SV_NODES_LOST], sl[SL_NODES_LOST]);
             } else if constexpr (FORCED) {
                 uint32_t forced = 0;
-                step_as<NOISE, true>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced);
+                step_as<NOISE, true, false, SYM>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full, fp, &forced);
                 if (forced) TAFL_COUNT_ADD(&fp->counters[FP_FORCED_SIMS], forced);
-            } else step_as<NOISE>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full);
+            } else step_as<NOISE, false, false, SYM>(M, g, priors, value, A, c_puct, n_sims, C, gs, NOISE ? &mine : nullptr, full);
             if (M.fault[g]) { sp.moves_done[g] = md | kGspStopped; return; }
             if (M.kind[g] == 1 || M.sims_done[g] < n_sims) return;           // its search goes on
             const GNode h = M.hdr[g];
@@ -684,11 +716,16 @@ struct Guided {
         selfplay_step_as<NOISE, EPISODES, true, true, true>(M, g, soa, priors, value, A, c_puct, n_sims, sp, rec, C, gs, NOISE ? &nz : nullptr, EPISODES ? &ep : nullptr, &pc, &fp, &sv);
     }
     // a fresh root that waits for its evaluation: what `step` leaves when it meets the unexpanded root of an ongoing game
-    static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) { init_game(M, g, root); M.kind[g] = 1; }
+    template <bool SYM = false>
+    static TAFL_HD void root_waits(const GuidedMem& M, uint32_t g, const S& root) {
+        init_game(M, g, root); M.kind[g] = 1;
+        if constexpr (SYM) leaf_symmetry(M, g, root);
+    }
     // Close and reopen (include/taflhip.h tafl_gselfplay_begin_episodes) for a lane that selfplay_step_episodes marked kGspEpisodeEnded: the
     // examples of the episode get their result when its game is over (examples_settle; a cut episode keeps z = 0, final = 0), the
     // result counters and the lane's episode number go up, the batch state becomes the opening and the new episode's root waits.  A
     // lane whose opening is over stops.  Returns true when a root now waits.
+    template <bool SYM = false>
     static TAFL_HD bool selfplay_reopen(const GuidedMem& M, uint32_t g, Quad* soa, const GSelfPlay& sp, const GEpisodes& ep, const SelfPlayRec& rec) {
         const uint32_t md = sp.moves_done[g];
         if (!(md & kGspEpisodeEnded) || (md & kGspStopped)) return false;
@@ -705,7 +742,7 @@ struct Guided {
         IO::load_soa(ep.openings, M.G, g, st);
         if (TAFL_F_STATUS(st.flags) != TAFL_STATUS_ONGOING) { sp.moves_done[g] = moves | kGspStopped; return false; }
         IO::store_soa(soa, M.G, g, st);
-        root_waits(M, g, st);
+        root_waits<SYM>(M, g, st);
         ep.ep_start[g] = moves; sp.moves_done[g] = moves;
         return true;
     }

@@ -238,6 +238,11 @@ struct tafl_batch {
     // Dirichlet noise at the root (tafl_gmcts_set_root_noise): the setting, and what the open search or run latched at its begin
     bool noise_set = false, g_noise_on = false;
     tafl_root_noise noise_cfg = {}; RootNoise g_noise = {};
+    // evaluation under a random board symmetry (tafl_gmcts_set_eval_symmetry): the setting; what the open search or run latched at its
+    // begin is gmem.sym (null: off) with its seed and game id base, over one byte per game
+    bool evalsym_set = false;
+    tafl_eval_symmetry evalsym_cfg = {};
+    DevBuf g_sym;
     // playout cap randomization (tafl_gselfplay_set_playout_cap): the setting, and what the guided self-play run that is open, or was last,
     // latched at its begin (gsp_cap_on: it is a capped run; its two class counters)
     bool cap_set = false, gsp_cap_on = false;
@@ -368,5 +373,21 @@ static int tree_advance(tafl_batch* b, const char* name, DevBuf& edges, DevBuf& 
     if (h_bad) return fail(TAFL_ERR_HIP, std::string(name) + ": a kept root differs from its new batch state (internal error; those games got fresh roots)");
     return TAFL_OK;
 }
+
+// ---- guided rounds: what tafl_gmcts.hip and tafl_gmcts_sym.hip share -------------------------------------------------------------------
+enum { GS_SIMS = 0, GS_PREDICTS, GS_TERMINAL, GS_FAULTS, GS_DEPTH, GS_WAITING, GS_COUNT };
+// what one lane's round adds to the counters of a step kernel
+static __device__ __forceinline__ void gstats_flush(const GuidedStats& gs, bool waiting, unsigned long long* stats) {
+    if (gs.sims) atomicAdd(&stats[GS_SIMS], (unsigned long long)gs.sims);
+    if (gs.predicts) atomicAdd(&stats[GS_PREDICTS], (unsigned long long)gs.predicts);
+    if (gs.terminal_hits) atomicAdd(&stats[GS_TERMINAL], (unsigned long long)gs.terminal_hits);
+    if (gs.faults) atomicAdd(&stats[GS_FAULTS], (unsigned long long)gs.faults);
+    if (gs.depth) atomicAdd(&stats[GS_DEPTH], (unsigned long long)gs.depth);
+    if (waiting) atomicAdd(&stats[GS_WAITING], 1ull);
+}
+// the rounds of a search or run that latched tafl_eval_symmetry (b->gmem.sym != nullptr): the SYM instantiations, in a translation unit
+// of their own (tafl_gmcts_sym.hip).  They take what tafl_gmcts_step / gselfplay_launch give their kernels and launch on the same stream.
+int gsym_launch_step(tafl_batch* b, const float* priors, const float* values, uint32_t A, double c_puct, uint32_t n_sims, unsigned long long* stats);
+int gsym_launch_selfplay(tafl_batch* b, const float* priors, const float* values, uint32_t A, unsigned long long* stats);
 
 #pragma GCC visibility pop

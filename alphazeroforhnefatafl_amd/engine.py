@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -455,6 +455,27 @@ class GameBatch:
 
     def clear_root_noise(self):
         check(lib().tafl_gmcts_set_root_noise(self._h, None))
+
+    # -- a random board symmetry per leaf evaluation (include/taflhip.h tafl_eval_symmetry) --------------------------------------
+    def set_eval_symmetry(self, seed: int, game_id_base: int = 0):
+        """Every leaf of every later gmcts_begin search and gselfplay run (latched at the begin) is shown to the evaluator under one of
+        the eight board symmetries, drawn from (seed, game id, position), and its priors are mapped back.  `game_id_base` keys a
+        lock-step search; a gselfplay run uses its own game ids.  A match refuses the setting."""
+        cfg = TaflEvalSymmetry(seed, game_id_base, 0)
+        check(lib().tafl_gmcts_set_eval_symmetry(self._h, C.byref(cfg)))
+
+    def clear_eval_symmetry(self):
+        check(lib().tafl_gmcts_set_eval_symmetry(self._h, None))
+
+    def gmcts_leaf_symmetry(self, out_device_ptr: int | None = None):
+        """The symmetry (0 .. 7) each waiting leaf is shown under, uint8 [n]; 0 for a game that does not wait and with the setting off
+        (tafl_gmcts_leaf_symmetry)."""
+        if out_device_ptr is not None:
+            check(lib().tafl_gmcts_leaf_symmetry(self._h, C.c_void_p(out_device_ptr), 1))
+            return None
+        out = (C.c_uint8 * self.n)()
+        check(lib().tafl_gmcts_leaf_symmetry(self._h, C.cast(out, C.c_void_p), 0))
+        return out
 
     # -- playout cap randomization of a guided self-play run (include/taflhip.h tafl_playout_cap) ------------------------------
     def set_playout_cap(self, fast_sims: int, full_prob: float, seed: int = 0):

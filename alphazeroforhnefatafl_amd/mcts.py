@@ -38,6 +38,10 @@ class MCTSArgs:
     forcedPlayoutsK: float = 0.0
     # exact win/loss proofs in the searches of a guided self-play run (include/taflhip.h tafl_solver)
     solver: bool = False
+    # every leaf of a guided search or self-play run is evaluated under a random board symmetry (include/taflhip.h tafl_eval_symmetry),
+    # drawn from (symmetrySeed, game id, position)
+    evalSymmetry: bool = False
+    symmetrySeed: int = 0
 
 
 def apply_root_noise(batch: GameBatch, args: MCTSArgs, move_no: int = 0):
@@ -70,6 +74,14 @@ def apply_solver(batch: GameBatch, args: MCTSArgs):
         batch.set_solver()
     else:
         batch.clear_solver()
+
+
+def apply_eval_symmetry(batch: GameBatch, args: MCTSArgs):
+    """The batch's eval-symmetry setting as `args` asks for it: set, or cleared."""
+    if args.evalSymmetry:
+        batch.set_eval_symmetry(args.symmetrySeed, args.game_id_base)
+    else:
+        batch.clear_eval_symmetry()
 
 
 _M32 = 0xFFFFFFFF
@@ -149,6 +161,7 @@ class GuidedMCTS:
     def search_all(self):
         a, b = self.args, self.batch
         apply_root_noise(b, a, self.move_no)           # (the noise of move number self.move_no: set it before each search of a game)
+        apply_eval_symmetry(b, a)
         b.gmcts_begin(a.numMCTSSims, self.edges_per_node, keep=self.keep_tree)
         waiting = b.gmcts_step(None, None, a.cpuct, a.numMCTSSims)
         while waiting:

@@ -9,7 +9,7 @@ import numpy as np
 
 from .abi import TaflState
 from .engine import Examples, GameBatch
-from .mcts import MCTSArgs, apply_forced_playouts, apply_playout_cap, apply_root_noise, apply_solver
+from .mcts import MCTSArgs, apply_eval_symmetry, apply_forced_playouts, apply_playout_cap, apply_root_noise, apply_solver
 
 
 class MatchResult:
@@ -53,11 +53,14 @@ def play_match(batch: GameBatch, nets, args: MCTSArgs, lane_moves: int, *, examp
         raise ValueError("play_match: a match takes no forced playouts (args.forcedPlayoutsK must be 0)")
     if args.solver:
         raise ValueError("play_match: a match takes no solver (args.solver must be False)")
+    if args.evalSymmetry:
+        raise ValueError("play_match: a match takes no eval symmetry (args.evalSymmetry must be False)")
     n = batch.n
     batch.clear_root_noise()
     batch.clear_playout_cap()
     batch.clear_forced_playouts()
     batch.clear_solver()
+    batch.clear_eval_symmetry()
     batch.gmatch_begin(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                        temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings, swap=swap)
     ptrs = None
@@ -129,6 +132,7 @@ def play_guided_episodes(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     apply_playout_cap(batch, args)
     apply_forced_playouts(batch, args)
     apply_solver(batch, args)
+    apply_eval_symmetry(batch, args)
     batch.gselfplay_begin(examples, max_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=args.game_id_base,
                           sample_seed=sample_seed, temp_moves=temp_moves, move_base=move_base)
     waiting = batch.gselfplay_step()
@@ -162,6 +166,7 @@ def play_guided_selfplay(batch: GameBatch, examples: Examples, nnet, args: MCTSA
     apply_playout_cap(batch, args)
     apply_forced_playouts(batch, args)
     apply_solver(batch, args)
+    apply_eval_symmetry(batch, args)
     batch.gselfplay_begin_episodes(examples, lane_moves, args.numMCTSSims, args.cpuct, edges_per_node, game_id_base=game_id_base, sample_seed=sample_seed,
                                    temp_moves=temp_moves, episode_moves=episode_moves, id_stride=id_stride, openings=openings)
     waiting = batch.gselfplay_step()

@@ -867,6 +867,46 @@ typedef struct tafl_solver_stats { uint64_t root_won, root_lost, skipped_sims, n
 int tafl_gselfplay_set_solver(tafl_batch* b, const tafl_solver* cfg);    /* NULL: off */
 int tafl_gselfplay_solver_stats(tafl_batch* b, tafl_solver_stats* out);
 
+/* ---- a random board symmetry per leaf evaluation in guided search and self-play ----------------------------------------
+ * Every ruleset of this library is invariant under the eight symmetries of the square (tafl_examples_gather serves training rows under
+ * them).  With this setting the evaluator is shown every leaf under a symmetry drawn for that leaf, and its policy is mapped back, as
+ * AlphaZero and KataGo do: over the visits of a search the network's orientation bias averages out, at no cost to the evaluator.
+ * Build-defined.  Off by default; with it off nothing in this header behaves differently and no new memory is read or written.
+ *
+ * Symmetry s (0 .. 7) is that of tafl_examples_gather: bit 2 transposes (r, c) -> (c, r) first, then bit 0 mirrors the rows, then bit 1
+ * the columns; sym_tile(s, t) and sym_action(s, a) are its action on tiles and on dense actions (from and to tile transformed).
+ *   the draw    for a leaf L that starts to wait for the evaluator in game g:  gid = game_id_base + g  (cfg's in a lock-step search, the
+ *               run's own in a tafl_gselfplay_* run, as for root noise),  h = the leaf key of L (the state hash the playouts are keyed by),
+ *                 s = ply_rand(sim_key(game_key(seed, gid) ^ 0x53594D4D45545259, h), 0) >> 29
+ *               (the taflmix32 family).  A pure function of (seed, gid, position): not of the lane, the batch size, the sharding or the
+ *               moment the search arrives, so the evaluator is still asked a function of the leaf it is shown, and a tafl_gselfplay run
+ *               still equals its per-move loop.  The episode number is not part of the key: in an episodes run the start position of
+ *               every episode of one lane draws the same s.
+ *   the input   tafl_gmcts_leaves writes the board byte of tile t of a waiting leaf to tile sym_tile(s, t) of the game's row.  sides and
+ *               waiting are unchanged, and so is the row of a game that does not wait.
+ *   the answer  when the leaf is expanded the prior of its legal action a is read from priors_row[sym_action(s, a)].  Everything after that
+ *               is unchanged and sees the legal actions in ascending original order: the masking multiply, the pairwise sum, the
+ *               all-masked branch, the root-noise mix (keyed by the original action), PUCT, forced playouts, the solver, the recording.
+ *               The value is used as delivered.
+ * So the search equals mcts.py run with predict'(b) = (unpermute_s(P), v) where (P, v) = predict(transform_s(b)).
+ *
+ * tafl_gmcts_set_eval_symmetry stores the setting on the batch (cfg == NULL: off).  tafl_gmcts_begin, tafl_gmcts_begin_ex (with
+ *   TAFL_GMCTS_KEEP_TREE too: the leaves of the continued search are drawn, the retained nodes keep their priors), tafl_gselfplay_begin and
+ *   tafl_gselfplay_begin_episodes latch it: a change during a search or run takes effect at the next begin.  Non-zero flags or _reserved:
+ *   TAFL_ERR_UNSUPPORTED (the setting is left as it was).  While it is set tafl_gmatch_begin fails with TAFL_ERR_UNSUPPORTED.
+ * tafl_gmcts_leaf_symmetry writes out_sym[g] = s of the leaf of game g that waits now, 0 for a game that does not wait and for every game
+ *   with the setting off [n bytes; out_is_device as in tafl_gmcts_leaves].  The step does not depend on this call or on tafl_gmcts_leaves.
+ * Not offered: matches, averaging one leaf over several symmetries, symmetry in rollout-mode search, a draw keyed by the move or episode
+ *   number, canonical positions. */
+typedef struct tafl_eval_symmetry {
+    uint64_t seed;
+    uint64_t game_id_base;   /* lock-step searches; a tafl_gselfplay run uses its own game_id_base */
+    uint32_t flags;          /* 0 */
+    uint32_t _reserved[3];   /* 0 */
+} tafl_eval_symmetry;        /* 32 bytes */
+int tafl_gmcts_set_eval_symmetry(tafl_batch* b, const tafl_eval_symmetry* cfg);      /* NULL: off (the default) */
+int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device);
+
 /* ---- training pool: a window over finished examples, sampled on the device ------------------------------------------
  * The piece between "self-play wrote examples" and "the trainer takes a minibatch": a fixed-capacity ring of finished examples in HBM that
  * outlives the tafl_examples objects it was filled from (alpha-zero-general keeps the examples of the last N iterations and trains on
