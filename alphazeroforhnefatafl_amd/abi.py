@@ -242,6 +242,17 @@ class TaflPoolIngestResult(C.Structure):
     _fields_ = [("taken", C.c_uint64), ("skipped_open", C.c_uint64), ("skipped_overflow", C.c_uint64), ("_reserved", C.c_uint64)]
 
 
+class TaflPoolWeights(C.Structure):
+    """tafl_pool_weights: the setting of weighted sampling (tafl_pool_set_weighting)."""
+    _fields_ = [("ingest_weight", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 6)]
+
+
+class TaflPoolWeightCounters(C.Structure):
+    """tafl_pool_weight_counters: what tafl_pool_weight_stats reports."""
+    _fields_ = [("enabled", C.c_uint64), ("ingest_weight", C.c_uint64), ("total_weight", C.c_uint64), ("positive", C.c_uint64),
+                ("bad_slot", C.c_uint64), ("rebuilds", C.c_uint64), ("device_bytes", C.c_uint64), ("_reserved", C.c_uint64)]
+
+
 POOL_SAMPLE_SYM = 0x1            # tafl_pool_sample flags: draw one of the eight symmetries per row
 
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
@@ -251,7 +262,7 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
                   "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
                   "tafl_eval_symmetry": 32,
-                  "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32}
+                  "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32, "tafl_pool_weights": 32, "tafl_pool_weight_counters": 64}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -262,7 +273,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_match_stats", TaflMatchStats), ("tafl_playout_cap", TaflPlayoutCap), ("tafl_playout_cap_stats", TaflPlayoutCapStats),
                     ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats),
                     ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats), ("tafl_eval_symmetry", TaflEvalSymmetry),
-                    ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult)]:
+                    ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult),
+                    ("tafl_pool_weights", TaflPoolWeights), ("tafl_pool_weight_counters", TaflPoolWeightCounters)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

@@ -144,6 +144,112 @@ __global__ __launch_bounds__(256) void k_pool_rows(PoolMem P, unsigned long long
     }
 }
 
+// ---- weighted sampling: per-slot weights, the tiles' prefix sums, the draw (tafl_pool.hpp: PoolWeights) ---------------------------------
+// every slot of [0, n) receives v (tafl_pool_set_weighting, off -> on; the padding beyond C too, it is never live)
+__global__ __launch_bounds__(256) void k_poolw_fill(uint32_t* wt, unsigned long long n, uint32_t v) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) wt[i] = v;
+}
+// Ingest, pass 4 (weighting on): the rows this ingest stored receive v.  res[0] = T as k_pool_scan left it.
+__global__ __launch_bounds__(256) void k_poolw_ingest(uint32_t* wt, const unsigned long long* res, unsigned long long written, uint32_t C, uint32_t v) {
+    const uint32_t T = (uint32_t)res[0], stored = T < C ? T : C;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < stored; i += (unsigned long long)gridDim.x * 256) wt[pool_stored_slot(written, (uint32_t)i, T, C)] = v;
+}
+// tafl_pool_set_weights, pass 1: 0 into every live slot named (a slot that is not live is skipped and counted, here only)
+__global__ __launch_bounds__(256) void k_poolw_zero(PoolWeights W, const uint32_t* slot, uint32_t count, uint32_t first, unsigned long long live, uint32_t C) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        if (pool_slot_live_from(s, first, live, C)) W.wt[s] = 0u;
+        else atomicAdd(&W.res[PW_BAD_SLOT], 1ull);
+    }
+}
+// pass 2: the maximum of the weights given for a slot, whatever the order
+__global__ __launch_bounds__(256) void k_poolw_max(PoolWeights W, const uint32_t* slot, const uint32_t* weight, uint32_t count, uint32_t first, unsigned long long live, uint32_t C) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        if (pool_slot_live_from(s, first, live, C)) atomicMax(&W.wt[s], weight[i]);
+    }
+}
+// tafl_pool_get_weights: 0 for a slot that is not live
+__global__ __launch_bounds__(256) void k_poolw_get(PoolWeights W, const uint32_t* slot, uint32_t count, uint32_t first, unsigned long long live, uint32_t C, uint32_t* out) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        out[i] = pool_slot_live_from(s, first, live, C) ? W.wt[s] : 0u;
+    }
+}
+// a lane's four consecutive slots 4 * lane .. 4 * lane + 3 of tile t (one 16-byte load), the weights of the dead ones masked away
+__device__ __forceinline__ void poolw_lane_eff(const PoolWeights& W, uint32_t t, uint32_t lane, uint32_t first, unsigned long long live, uint32_t C, uint32_t e[POOLW_PER_LANE]) {
+    const uint4 v = reinterpret_cast<const uint4*>(W.wt)[(size_t)t * POOLW_LANES + lane];
+    const uint32_t s0 = t * (uint32_t)POOLW_TILE + lane * (uint32_t)POOLW_PER_LANE;
+    e[0] = pool_eff(v.x, s0, first, live, C); e[1] = pool_eff(v.y, s0 + 1u, first, live, C);
+    e[2] = pool_eff(v.z, s0 + 2u, first, live, C); e[3] = pool_eff(v.w, s0 + 3u, first, live, C);
+}
+// Rebuild, pass 1: one wave per tile of 256 slots (four tiles per workgroup): the tile's sum of eff and its count of positive live slots
+__global__ __launch_bounds__(256) void k_poolw_tiles(PoolWeights W, uint32_t first, unsigned long long live, uint32_t C) {
+    const uint32_t lane = threadIdx.x & 63u, t = blockIdx.x * 4u + (threadIdx.x >> 6);
+    if (t >= W.NT) return;                                                     // (wave-uniform)
+    uint32_t e[POOLW_PER_LANE];
+    poolw_lane_eff(W, t, lane, first, live, C, e);
+    unsigned long long sum = (unsigned long long)e[0] + e[1] + e[2] + e[3];
+    uint32_t pos = (e[0] != 0u) + (e[1] != 0u) + (e[2] != 0u) + (e[3] != 0u);
+    for (uint32_t d = 32; d; d >>= 1) { sum += __shfl_xor(sum, d, 64); pos += __shfl_xor(pos, d, 64); }
+    if (lane == 0) { W.tile_sum[t] = sum; W.tile_pos[t] = pos; }
+}
+// Rebuild, pass 2: the exclusive prefix of the tiles' sums in 64 bits, by one workgroup that walks them 256 at a time with a carry as
+// k_pool_scan does (no width limit), and res = { total, positive live slots }
+__global__ __launch_bounds__(256) void k_poolw_scan(PoolWeights W) {
+    __shared__ unsigned long long wave_tot[4], pos_tot[4];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    unsigned long long carry = 0, positive = 0;
+    for (uint32_t c0 = 0; c0 < W.NT; c0 += 256) {
+        const uint32_t i = c0 + threadIdx.x;
+        const unsigned long long v = i < W.NT ? W.tile_sum[i] : 0ull;
+        unsigned long long pos = i < W.NT ? W.tile_pos[i] : 0ull;
+        unsigned long long incl = v;
+        for (uint32_t d = 1; d < 64; d <<= 1) { const unsigned long long u = __shfl_up(incl, d, 64); if (lane >= d) incl += u; }
+        for (uint32_t d = 32; d; d >>= 1) pos += __shfl_xor(pos, d, 64);
+        if (lane == 63) { wave_tot[wave] = incl; pos_tot[wave] = pos; }
+        __syncthreads();
+        unsigned long long before = 0, total = 0;
+        for (uint32_t w = 0; w < 4; ++w) { const unsigned long long c = wave_tot[w]; if (w < wave) before += c; total += c; positive += pos_tot[w]; }
+        if (i < W.NT) W.tile_pre[i] = carry + before + incl - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) { W.res[PW_TOTAL] = carry; W.res[PW_POSITIVE] = positive; }
+}
+// The weighted draw, one wave per row: the tile by pool_wsearch_* (64 prefixes per load, a ballot per step), then inside the tile a
+// wave scan of the lanes' sums of four weights, a ballot for the lane and pool_wpick for the slot.  total > 0.
+__global__ __launch_bounds__(256) void k_poolw_draw(PoolWeights W, uint32_t first, unsigned long long live, uint32_t C, unsigned long long seed, unsigned long long step,
+                                                    uint32_t row_base, uint32_t flags, uint32_t count, unsigned long long total, uint32_t* out_slot, uint8_t* out_sym,
+                                                    uint32_t* out_weight) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 4u + (threadIdx.x >> 6); i < count; i += (unsigned long long)gridDim.x * 4u) {      // (wave-uniform)
+        uint64_t k; uint32_t sym;
+        pool_wdraw(seed, step, row_base + (uint32_t)i, total, flags, k, sym);
+        uint32_t lo = 0, hi = W.NT;
+        while (hi - lo > 1u) {
+            uint32_t idx;
+            const bool in = pool_wsearch_probe(lo, hi, lane, idx);
+            const bool le = in && W.tile_pre[idx] <= k;
+            pool_wsearch_narrow(lo, hi, (uint32_t)__popcll(__ballot(le)));
+        }
+        uint32_t e[POOLW_PER_LANE];
+        poolw_lane_eff(W, lo, lane, first, live, C, e);
+        const unsigned long long sum = (unsigned long long)e[0] + e[1] + e[2] + e[3], kk = k - W.tile_pre[lo];
+        unsigned long long incl = sum;
+        for (uint32_t d = 1; d < 64; d <<= 1) { const unsigned long long u = __shfl_up(incl, d, 64); if (lane >= d) incl += u; }
+        const unsigned long long excl = incl - sum;
+        const uint32_t c = (uint32_t)__popcll(__ballot(excl <= kk)), L = c ? c - 1u : 0u;      // (excl ascends over the lanes, lane 0 holds 0)
+        if (lane == L) {
+            uint32_t w;
+            const uint32_t j = pool_wpick(e[0], e[1], e[2], e[3], kk - excl, w);
+            out_slot[i] = lo * (uint32_t)POOLW_TILE + L * (uint32_t)POOLW_PER_LANE + j;
+            out_sym[i] = (uint8_t)sym;
+            out_weight[i] = w;
+        }
+    }
+}
+
 struct tafl_pool {
     tafl_ctx* ctx;
     PoolMem mem;
@@ -153,6 +259,19 @@ struct tafl_pool {
     DevBuf g_slot, g_sym, g_boards, g_sides, g_pi, g_z;      // staging of calls with host pointers
     size_t device_bytes = 0;
     int need(DevBuf& d, size_t bytes) { device_bytes -= d.cap; const int rc = d.ensure(bytes); device_bytes += d.cap; return rc; }
+    // weighted sampling (off: no buffer of it exists)
+    bool weighting = false, dirty = true;
+    uint32_t ingest_weight = 0;
+    uint64_t total = 0, positive = 0, rebuilds = 0;          // total, positive: as of the last rebuild
+    PoolWeights wmem{};
+    DevBuf wt, wtiles, wres, w_slot, w_sym, w_weight;        // w_*: the draw and its staging
+    size_t weight_bytes = 0;
+    int wneed(DevBuf& d, size_t bytes) { const size_t before = d.cap; const int rc = need(d, bytes); weight_bytes += d.cap - before; return rc; }
+    void wfree() {
+        for (DevBuf* d : {&wt, &wtiles, &wres, &w_slot, &w_sym, &w_weight}) { device_bytes -= d->cap; d->release(); }
+        weight_bytes = 0; weighting = false; wmem = PoolWeights{};
+    }
+    uint32_t first_live() const { return book.live ? pool_first_live(book.written, book.live, mem.C) : 0u; }
 };
 
 #define POOLCHK(p, name) do { if (!(p)) return fail(TAFL_ERR_INVALID_ARG, name ": null pool"); HIPCHK(hipSetDevice((p)->ctx->device)); } while (0)
@@ -238,7 +357,9 @@ int tafl_pool_destroy(tafl_pool* p) {
 int tafl_pool_clear(tafl_pool* p) {
     POOLCHK(p, "tafl_pool_clear");
     HIPCHK(hipMemsetAsync(p->counters.p, 0, 8 * POOL_COUNTERS, p->ctx->stream));
+    if (p->weighting) HIPCHK(hipMemsetAsync(p->wres.p, 0, 8 * PW_WORDS, p->ctx->stream));
     p->book.clear(); p->skipped_open = p->skipped_overflow = 0;
+    p->dirty = true; p->total = p->positive = p->rebuilds = 0;          // (the setting of the weighting and the stored weights stay)
     return sync_ok(p->ctx);
 }
 int tafl_pool_get_stats(tafl_pool* p, tafl_pool_stats* out) {
@@ -270,6 +391,11 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     hipLaunchKernelGGL(k_pool_scan, dim3(1), dim3(POOL_TILE), 0, s, (const uint32_t*)taken, (const uint32_t*)open, (const uint32_t*)over, nb, prefix, res);
     hipLaunchKernelGGL(k_pool_copy, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, E, p->mem, (const uint32_t*)prefix, (const unsigned long long*)res,
                        (unsigned long long)p->book.written, generation);
+    if (p->weighting) {
+        const uint32_t most = E < p->mem.C ? E : p->mem.C, grid = std::min<uint32_t>((most + 255u) / 256u, 2048u);       // (T <= E rows at most)
+        if (grid) hipLaunchKernelGGL(k_poolw_ingest, dim3(grid), dim3(256), 0, s, p->wmem.wt, (const unsigned long long*)res, (unsigned long long)p->book.written, p->mem.C, p->ingest_weight);
+        p->dirty = true;
+    }
     HIPCHK(hipGetLastError());
     unsigned long long h[3];
     HIPCHK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, s));
@@ -283,6 +409,7 @@ int tafl_pool_trim(tafl_pool* p, uint32_t keep_generations) {
     POOLCHK(p, "tafl_pool_trim");
     if (keep_generations == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_trim: keep_generations must be at least 1");
     p->book.trim(keep_generations);
+    p->dirty = true;
     return TAFL_OK;
 }
 
@@ -333,6 +460,178 @@ int tafl_pool_read(tafl_pool* p, const uint32_t* slot, uint32_t count, uint32_t*
             if (visits) visits[(size_t)i * Kp + k] = w >> 16;
         }
     }
+    return TAFL_OK;
+}
+
+}  // extern "C"
+
+// ---- weighted sampling ---------------------------------------------------------------------------------------------------------------------
+static uint32_t poolw_grid(uint64_t items) { return (uint32_t)std::min<uint64_t>((items + 255u) / 256u, 2048u); }
+// the tiles' sums and prefixes follow the weights and the live window again; total and positive come back (16 bytes)
+static int poolw_rebuild(tafl_pool* p) {
+    if (!p->dirty) return TAFL_OK;
+    hipStream_t s = p->ctx->stream;
+    const uint32_t first = p->first_live();
+    hipLaunchKernelGGL(k_poolw_tiles, dim3((p->wmem.NT + 3u) / 4u), dim3(256), 0, s, p->wmem, first, (unsigned long long)p->book.live, p->mem.C);
+    hipLaunchKernelGGL(k_poolw_scan, dim3(1), dim3(256), 0, s, p->wmem);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[2];
+    HIPCHK(hipMemcpyAsync(h, p->wres.p, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    p->total = h[PW_TOTAL]; p->positive = h[PW_POSITIVE]; p->rebuilds += 1; p->dirty = false;
+    return TAFL_OK;
+}
+// the slots (and weights) of a call in device memory: the caller's own arrays, or copies of the host's in the weighting's staging
+static int poolw_stage_in(tafl_pool* p, const uint32_t*& slot, const uint32_t*& weight, uint32_t count, int ptrs_are_device, const char* name) {
+    if (ptrs_are_device) return TAFL_OK;
+    for (uint32_t i = 0; i < count; ++i)
+        if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, std::string(name) + ": slot " + std::to_string(slot[i]) + " (entry " + std::to_string(i) + ") is not live");
+    if (p->wneed(p->w_slot, 4 * (size_t)count)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed");
+    HIPCHK(hipMemcpyAsync(p->w_slot.p, slot, 4 * (size_t)count, hipMemcpyHostToDevice, p->ctx->stream));
+    slot = p->w_slot.as<const uint32_t>();
+    if (weight) {
+        if (p->wneed(p->w_weight, 4 * (size_t)count)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed");
+        HIPCHK(hipMemcpyAsync(p->w_weight.p, weight, 4 * (size_t)count, hipMemcpyHostToDevice, p->ctx->stream));
+        weight = p->w_weight.as<const uint32_t>();
+    }
+    return TAFL_OK;
+}
+
+extern "C" {
+
+int tafl_pool_set_weighting(tafl_pool* p, const tafl_pool_weights* w) {
+    POOLCHK(p, "tafl_pool_set_weighting");
+    hipStream_t s = p->ctx->stream;
+    if (!w) {
+        HIPCHK(hipStreamSynchronize(s));
+        p->wfree(); p->dirty = true; p->total = p->positive = p->rebuilds = 0;
+        return TAFL_OK;
+    }
+    if (w->flags) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_set_weighting: flags must be 0");
+    for (uint32_t r : w->_reserved) if (r) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_set_weighting: reserved words must be 0");
+    if (!p->weighting) {
+        const uint32_t NT = pool_weight_tiles(p->mem.C);
+        const size_t slots = (size_t)NT * POOLW_TILE;
+        // tile_sum, tile_pre (8 bytes each), then tile_pos (4 bytes) per tile
+        if (p->wneed(p->wt, 4 * slots) || p->wneed(p->wtiles, 20 * (size_t)NT) || p->wneed(p->wres, 8 * PW_WORDS)) {
+            p->wfree();
+            return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_pool_set_weighting)");
+        }
+        PoolWeights& W = p->wmem;
+        W.NT = NT; p->wt.bind(W.wt); p->wres.bind(W.res);
+        W.tile_sum = p->wtiles.as<unsigned long long>(); W.tile_pre = W.tile_sum + NT; W.tile_pos = reinterpret_cast<uint32_t*>(W.tile_pre + NT);
+        HIPCHK(hipMemsetAsync(p->wres.p, 0, 8 * PW_WORDS, s));
+        hipLaunchKernelGGL(k_poolw_fill, dim3(poolw_grid(slots)), dim3(256), 0, s, W.wt, (unsigned long long)slots, w->ingest_weight);
+        HIPCHK(hipGetLastError());
+        p->weighting = true; p->rebuilds = 0;
+    }
+    p->ingest_weight = w->ingest_weight;
+    p->dirty = true;
+    return sync_ok(p->ctx);
+}
+
+int tafl_pool_set_weights(tafl_pool* p, const uint32_t* slot, const uint32_t* weight, uint32_t count, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_set_weights");
+    if (!p->weighting) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_set_weights: weighting is off (tafl_pool_set_weighting)");
+    if ((!slot || !weight) && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_set_weights: null argument");
+    if (count == 0) return TAFL_OK;
+    const int rc = poolw_stage_in(p, slot, weight, count, ptrs_are_device, "tafl_pool_set_weights");
+    if (rc) return rc;
+    hipStream_t s = p->ctx->stream;
+    const uint32_t first = p->first_live(), grid = poolw_grid(count);
+    hipLaunchKernelGGL(k_poolw_zero, dim3(grid), dim3(256), 0, s, p->wmem, slot, count, first, (unsigned long long)p->book.live, p->mem.C);
+    hipLaunchKernelGGL(k_poolw_max, dim3(grid), dim3(256), 0, s, p->wmem, slot, weight, count, first, (unsigned long long)p->book.live, p->mem.C);
+    HIPCHK(hipGetLastError());
+    p->dirty = true;
+    if (!ptrs_are_device) HIPCHK(hipStreamSynchronize(s));
+    return TAFL_OK;
+}
+
+int tafl_pool_get_weights(tafl_pool* p, const uint32_t* slot, uint32_t count, uint32_t* weight, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_get_weights");
+    if (!p->weighting) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_get_weights: weighting is off (tafl_pool_set_weighting)");
+    if ((!slot || !weight) && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_get_weights: null argument");
+    if (count == 0) return TAFL_OK;
+    const uint32_t* none = nullptr;
+    const int rc = poolw_stage_in(p, slot, none, count, ptrs_are_device, "tafl_pool_get_weights");
+    if (rc) return rc;
+    hipStream_t s = p->ctx->stream;
+    uint32_t* out = weight;
+    if (!ptrs_are_device) { if (p->wneed(p->w_weight, 4 * (size_t)count)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed"); out = p->w_weight.as<uint32_t>(); }
+    hipLaunchKernelGGL(k_poolw_get, dim3(poolw_grid(count)), dim3(256), 0, s, p->wmem, slot, count, p->first_live(), (unsigned long long)p->book.live, p->mem.C, out);
+    HIPCHK(hipGetLastError());
+    if (!ptrs_are_device) { COPY_OUT(weight, out, count, s); HIPCHK(hipStreamSynchronize(s)); }
+    return TAFL_OK;
+}
+
+int tafl_pool_sample_weighted(tafl_pool* p, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t count, uint32_t flags, uint8_t* boards, uint8_t* sides, float* pi, float* z,
+                              uint32_t* out_slot, uint8_t* out_sym, uint32_t* out_weight, uint64_t* out_total, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_sample_weighted");
+    if (flags & ~(uint32_t)TAFL_POOL_SAMPLE_SYM) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_sample_weighted: unknown flag bits");
+    if (!p->weighting) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample_weighted: weighting is off (tafl_pool_set_weighting)");
+    if ((unsigned long long)row_base + count > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample_weighted: row_base + count exceeds 32 bits");
+    if (p->book.live == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample_weighted: the pool holds no live row");
+    int rc = poolw_rebuild(p);
+    if (rc) return rc;
+    if (p->total == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_sample_weighted: every live row has weight 0");
+    tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
+    if (out_total) {                                         // (one uint64, also with device pointers)
+        if (ptrs_are_device) HIPCHK(hipMemcpyAsync(out_total, p->wres.as<unsigned long long>() + PW_TOTAL, 8, hipMemcpyDeviceToDevice, s));
+        else *out_total = p->total;
+    }
+    if (count == 0) return TAFL_OK;
+    const uint32_t first = p->first_live();
+    auto draw = [&](uint32_t base, uint32_t k, uint32_t* d_slot, uint8_t* d_sym, uint32_t* d_weight) {
+        const uint32_t grid = std::min<uint32_t>((k + 3u) / 4u, 4096u);
+        hipLaunchKernelGGL(k_poolw_draw, dim3(grid), dim3(256), 0, s, p->wmem, first, (unsigned long long)p->book.live, p->mem.C, (unsigned long long)seed, (unsigned long long)step,
+                           base, flags, k, (unsigned long long)p->total, d_slot, d_sym, d_weight);
+    };
+    // the draw needs somewhere to write: what the caller did not ask for goes to the weighting's staging
+    const uint32_t chunk = ptrs_are_device ? count : (count < 8192u ? count : 8192u);
+    uint32_t* d_slot = out_slot; uint8_t* d_sym = out_sym; uint32_t* d_weight = out_weight;
+    if (!ptrs_are_device || !out_slot) { if (p->wneed(p->w_slot, 4 * (size_t)chunk)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed"); d_slot = p->w_slot.as<uint32_t>(); }
+    if (!ptrs_are_device || !out_sym) { if (p->wneed(p->w_sym, chunk)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed"); d_sym = p->w_sym.as<uint8_t>(); }
+    if (!ptrs_are_device || !out_weight) { if (p->wneed(p->w_weight, 4 * (size_t)chunk)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed"); d_weight = p->w_weight.as<uint32_t>(); }
+    if (ptrs_are_device) {
+        draw(row_base, count, d_slot, d_sym, d_weight);
+        HIPCHK(hipGetLastError());
+        return pool_rows_launch(p, false, 0, 0, 0, 0, d_slot, d_sym, count, boards, sides, pi, z, nullptr, nullptr);
+    }
+    const size_t A = (size_t)c->n * c->n * 2u * (c->n - 1u), nn = (size_t)c->n * c->n;
+    POOLNEED(p->g_sides, chunk); POOLNEED(p->g_z, 4 * (size_t)chunk);
+    if (boards) POOLNEED(p->g_boards, nn * chunk);
+    if (pi) POOLNEED(p->g_pi, 4 * A * chunk);
+    for (uint32_t i0 = 0; i0 < count; i0 += chunk) {
+        const uint32_t k = count - i0 < chunk ? count - i0 : chunk;
+        draw(row_base + i0, k, d_slot, d_sym, d_weight);
+        HIPCHK(hipGetLastError());
+        rc = pool_rows_launch(p, false, 0, 0, 0, 0, d_slot, d_sym, k, boards ? p->g_boards.as<uint8_t>() : nullptr, sides ? p->g_sides.as<uint8_t>() : nullptr,
+                              pi ? p->g_pi.as<float>() : nullptr, z ? p->g_z.as<float>() : nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        if (boards) COPY_OUT(boards + (size_t)i0 * nn, p->g_boards.p, nn * k, s);
+        if (sides) COPY_OUT(sides + i0, p->g_sides.p, k, s);
+        if (pi) COPY_OUT(pi + (size_t)i0 * A, p->g_pi.p, A * k, s);
+        if (z) COPY_OUT(z + i0, p->g_z.p, k, s);
+        if (out_slot) COPY_OUT(out_slot + i0, d_slot, k, s);
+        if (out_sym) COPY_OUT(out_sym + i0, d_sym, k, s);
+        if (out_weight) COPY_OUT(out_weight + i0, d_weight, k, s);
+        HIPCHK(hipStreamSynchronize(s));
+    }
+    return TAFL_OK;
+}
+
+int tafl_pool_weight_stats(tafl_pool* p, tafl_pool_weight_counters* out) {
+    POOLCHK(p, "tafl_pool_weight_stats");
+    if (!out) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weight_stats: null argument");
+    memset(out, 0, sizeof *out);
+    if (!p->weighting) return TAFL_OK;
+    const int rc = poolw_rebuild(p);
+    if (rc) return rc;
+    unsigned long long bad = 0;
+    HIPCHK(hipMemcpyAsync(&bad, p->wres.as<unsigned long long>() + PW_BAD_SLOT, 8, hipMemcpyDeviceToHost, p->ctx->stream));
+    HIPCHK(hipStreamSynchronize(p->ctx->stream));
+    out->enabled = 1; out->ingest_weight = p->ingest_weight; out->total_weight = p->total; out->positive = p->positive; out->bad_slot = bad;
+    out->rebuilds = p->rebuilds; out->device_bytes = p->weight_bytes;
     return TAFL_OK;
 }
 

@@ -1,9 +1,10 @@
 // tafl_pool.hpp — the training pool (tafl_pool_*): a ring of finished training examples in HBM, filled from a
 // tafl_examples object and sampled uniformly under random board symmetries.  What is decided per example, per row and per drawn row is
 // here: which recorded example an ingest takes (pool_take), the words of a row (pool_row_word), the draw (pool_draw), which slots are
-// live (pool_slot_live) and what a row writes into a minibatch (pool_out_tile, pool_out_pi).  __host__ __device__ like tafl_examples.hpp:
-// the kernels of tafl_pool.hip run these functions one example / word / tile / policy entry per lane, tests/hostsim_pool runs them in
-// serial loops on the CPU.
+// live (pool_slot_live) and what a row writes into a minibatch (pool_out_tile, pool_out_pi); for weighted sampling the masked weight
+// (pool_eff), the weighted draw (pool_wdraw) and the steps of its search (pool_wsearch_*, pool_wpick).  __host__ __device__ like
+// tafl_examples.hpp: the kernels of tafl_pool.hip run these functions one example / word / tile / policy entry / probe per lane,
+// tests/hostsim_pool and tests/hostsim_pool_weights run them in serial loops on the CPU.
 #pragma once
 #include <vector>
 #include "tafl_examples.hpp"
@@ -88,6 +89,71 @@ static TAFL_HD float pool_out_pi(const uint32_t* row, uint32_t BW, uint32_t k, u
 static TAFL_HD uint32_t pool_row_children(const uint32_t* row, uint32_t BW) { return row[BW + (uint32_t)PR_INFO] & 0xFFFFu; }
 static TAFL_HD uint8_t pool_row_side(const uint32_t* row, uint32_t BW) { return (uint8_t)((row[BW + (uint32_t)PR_INFO] >> 16) & 0xFFu); }
 static TAFL_HD float pool_row_z(const uint32_t* row, uint32_t BW) { union { float f; uint32_t u; } c; c.u = row[BW + (uint32_t)PR_Z]; return c.f; }
+
+// ---- weighted sampling (tafl_pool_set_weighting / _set_weights / _sample_weighted): one uint32 weight per slot, a draw in proportion ----
+// eff(s) = wt[s] where slot s is live, else 0; W(s) = the sum of eff below s in SLOT order (64 bits), total = W(C).  The prefix structure
+// holds, per tile of POOLW_TILE slots, the sum of eff and the exclusive prefix of the sums; a draw searches the tiles' prefixes 64 at a
+// time (one probe per lane of a wave), then the 256 weights of the tile, four per lane.
+constexpr uint64_t kPoolWDrawKey = 0x504F4F4C57445257ull;     // "POOLWDRW"
+enum { POOLW_TILE = 256, POOLW_LANES = 64, POOLW_PER_LANE = 4 };
+enum { PW_TOTAL = 0, PW_POSITIVE = 1, PW_BAD_SLOT = 2, PW_WORDS = 3 };
+struct PoolWeights {
+    uint32_t* wt;                    // [NT * POOLW_TILE]: the slots C .. NT * POOLW_TILE - 1 are never live
+    unsigned long long* tile_sum;    // [NT]
+    unsigned long long* tile_pre;    // [NT] exclusive
+    uint32_t* tile_pos;              // [NT] live slots of the tile with a weight above 0
+    unsigned long long* res;         // [PW_WORDS]
+    uint32_t NT;
+};
+static TAFL_HD uint32_t pool_weight_tiles(uint32_t C) { return (uint32_t)(((uint64_t)C + POOLW_TILE - 1) / POOLW_TILE); }
+// pool_slot_live with the first live slot, (written - live) mod C, worked out once
+static TAFL_HD uint32_t pool_first_live(uint64_t written, uint64_t live, uint32_t C) { return (uint32_t)((written - live) % C); }
+static TAFL_HD bool pool_slot_live_from(uint32_t s, uint32_t first, uint64_t live, uint32_t C) {
+    if (s >= C) return false;
+    const uint64_t age = s >= first ? (uint64_t)(s - first) : (uint64_t)s + (C - first);
+    return age < live;
+}
+static TAFL_HD uint32_t pool_eff(uint32_t w, uint32_t s, uint32_t first, uint64_t live, uint32_t C) { return pool_slot_live_from(s, first, live, C) ? w : 0u; }
+// the high 64 bits of a * b
+static TAFL_HD uint64_t pool_mulhi64(uint64_t a, uint64_t b) {
+    const uint64_t a0 = (uint32_t)a, a1 = a >> 32, b0 = (uint32_t)b, b1 = b >> 32;
+    const uint64_t p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const uint64_t mid = (p00 >> 32) + (uint32_t)p01 + (uint32_t)p10;
+    return p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+}
+// the weighted draw of row `row` of the sample (seed, step): k < total, the slot is the one s with W(s) <= k < W(s) + eff(s)
+static TAFL_HD void pool_wdraw(uint64_t seed, uint64_t step, uint32_t row, uint64_t total, uint32_t flags, uint64_t& k, uint32_t& sym) {
+    using E = Engine<2, 7>;
+    const uint32_t dk = E::sim_key(E::game_key(seed, step) ^ kPoolWDrawKey, row);
+    const uint64_t r = (uint64_t)E::ply_rand(dk, 2u) << 32 | E::ply_rand(dk, 3u);
+    k = pool_mulhi64(r, total);
+    sym = (flags & 1u) ? E::ply_rand(dk, 1u) >> 29 : 0u;
+}
+// The search for the last tile t of [lo, hi) with tile_pre[t] <= k (tile_pre[lo] <= k holds), 64 probes per step: lane `lane` probes
+// lo + lane * stride; the prefixes ascend, so the lanes whose probe is inside the range and <= k are the first c >= 1 lanes, and the tile
+// lies in the stride behind the last of them.  hi - lo shrinks to at most ceil((hi - lo) / 64) per step: three steps for 16 384 tiles.
+static TAFL_HD uint32_t pool_wsearch_stride(uint32_t lo, uint32_t hi) { return (hi - lo + (uint32_t)POOLW_LANES - 1u) / (uint32_t)POOLW_LANES; }
+static TAFL_HD bool pool_wsearch_probe(uint32_t lo, uint32_t hi, uint32_t lane, uint32_t& idx) {
+    const uint64_t i = (uint64_t)lo + (uint64_t)lane * pool_wsearch_stride(lo, hi);
+    idx = (uint32_t)i;
+    return i < hi;
+}
+static TAFL_HD void pool_wsearch_narrow(uint32_t& lo, uint32_t& hi, uint32_t c) {
+    const uint32_t stride = pool_wsearch_stride(lo, hi);
+    lo += ((c ? c : 1u) - 1u) * stride;
+    if (hi - lo > stride) hi = lo + stride;
+}
+// inside a lane's four slots: the last j whose weights below it sum to at most `rem` (rem < the lane's sum); w = that slot's weight
+static TAFL_HD uint32_t pool_wpick(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, uint64_t rem, uint32_t& w) {
+    const uint64_t p1 = e0, p2 = p1 + e1, p3 = p2 + e2;
+    uint32_t j = 0; w = e0;
+    if (p1 <= rem) { j = 1; w = e1; }
+    if (p2 <= rem) { j = 2; w = e2; }
+    if (p3 <= rem) { j = 3; w = e3; }
+    return j;
+}
+// the slot the rank i < min(T, C) of the rows an ingest of T taken examples stores goes to (the ranks r >= T - min(T, C), pool_place)
+static TAFL_HD uint32_t pool_stored_slot(uint64_t written, uint32_t i, uint32_t T, uint32_t C) { return (uint32_t)((written + (T - (T < C ? T : C)) + i) % C); }
 
 
 // The host's bookkeeping of a pool (tafl_pool_ingest, tafl_pool_trim, tafl_pool_get_stats): the live rows are [written - live, written),

@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -806,6 +806,91 @@ class Pool:
         out = self._outputs(k, False)
         check(lib().tafl_pool_gather(self._h, sl.ctypes.data_as(vp), sy.ctypes.data_as(vp) if sy is not None else None, k, *[a.ctypes.data_as(vp) for a in out], 0))
         return out
+
+    # ---- weighted sampling (tafl_pool_set_weighting / _set_weights / _get_weights / _sample_weighted / _weight_stats) ----
+    def set_weighting(self, ingest_weight):
+        """Switches weighted sampling on: one uint32 weight per slot, `ingest_weight` for every slot now (if it was off) and for every row
+        a later ingest stores.  None switches it off and frees its buffers (the default: the pool behaves and allocates as without it)."""
+        if ingest_weight is None:
+            check(lib().tafl_pool_set_weighting(self._h, None))
+            return
+        w = TaflPoolWeights(ingest_weight=ingest_weight)
+        check(lib().tafl_pool_set_weighting(self._h, C.byref(w)))
+
+    def _device_u32(self, t, what, k=None):
+        import torch
+        t = t.contiguous()
+        if t.dtype != torch.int32 or not t.is_cuda or t.device.index != self.logic.device or (k is not None and t.numel() != k):
+            raise ValueError(f"{what} must be an int32 tensor on the context's device" + ("" if k is None else ", one per slot"))
+        return t
+
+    def set_weights(self, slots, weights, device: bool = False):
+        """Every live slot named holds the maximum of the weights given for it afterwards (duplicates in any order); 0 silences a row.
+        device=False: sequences or numpy arrays; a slot that is not live raises before anything is written.  device=True: int32 torch
+        tensors on the context's device (the bits of a uint32); such an entry is skipped and counts in weight_stats().bad_slot."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            sl = self._device_u32(slots, "set_weights(device=True): slots")
+            wt = self._device_u32(weights, "set_weights(device=True): weights", int(sl.numel()))
+            torch.cuda.current_stream(sl.device).synchronize()          # the library works on its own stream
+            check(lib().tafl_pool_set_weights(self._h, vp(sl.data_ptr()), vp(wt.data_ptr()), int(sl.numel()), 1))
+            self.logic.sync()
+            return
+        import numpy as np
+        sl, wt = np.ascontiguousarray(slots, dtype=np.uint32), np.ascontiguousarray(weights, dtype=np.uint32)
+        if sl.size != wt.size:
+            raise ValueError("set_weights: one weight per slot")
+        check(lib().tafl_pool_set_weights(self._h, sl.ctypes.data_as(vp), wt.ctypes.data_as(vp), int(sl.size), 0))
+
+    def weights(self, slots):
+        """The weights of `slots`: a numpy uint32 array for a sequence or numpy array (a slot that is not live raises), an int32 tensor for an
+        int32 tensor on the context's device (0 for a slot that is not live)."""
+        vp = C.c_void_p
+        if hasattr(slots, "data_ptr"):
+            import torch
+            sl = self._device_u32(slots, "weights: a slot tensor")
+            out = torch.empty_like(sl)
+            torch.cuda.current_stream(sl.device).synchronize()
+            check(lib().tafl_pool_get_weights(self._h, vp(sl.data_ptr()), int(sl.numel()), vp(out.data_ptr()), 1))
+            self.logic.sync()
+            return out
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        out = np.zeros(sl.size, np.uint32)
+        check(lib().tafl_pool_get_weights(self._h, sl.ctypes.data_as(vp), int(sl.size), out.ctypes.data_as(vp), 0))
+        return out
+
+    def sample_weighted(self, count: int, seed: int, step: int, row_base: int = 0, symmetries: bool = True, device: bool = False):
+        """`count` live rows drawn with replacement in proportion to their weights, as (boards, sides, pi, z, slot, sym, weight, total) in the
+        shapes of `sample`: weight[i] is the weight of the row drawn, total (an int) the sum over the live rows, so weight / total is
+        the probability the row was drawn with.  Row i depends on (seed, step, row_base + i), the live window and the weights alone."""
+        flags = abi.POOL_SAMPLE_SYM if symmetries else 0
+        vp = C.c_void_p
+        if device:
+            import torch
+            dev = torch.device("cuda", self.logic.device)
+            out = self._outputs(count, True, dev)
+            slot, sym = torch.empty((count,), dtype=torch.int32, device=dev), torch.empty((count,), dtype=torch.uint8, device=dev)
+            weight, total = torch.empty((count,), dtype=torch.int32, device=dev), torch.zeros((1,), dtype=torch.int64, device=dev)
+            torch.cuda.current_stream(dev).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_sample_weighted(self._h, seed, step, row_base, count, flags, *[vp(t.data_ptr()) for t in out], vp(slot.data_ptr()), vp(sym.data_ptr()),
+                                                  vp(weight.data_ptr()), vp(total.data_ptr()), 1))
+            self.logic.sync()
+            return (*out, slot, sym, weight, int(total.item()) & 0xFFFFFFFFFFFFFFFF)
+        import numpy as np
+        out = self._outputs(count, False)
+        slot, sym, weight = np.zeros((count,), np.uint32), np.zeros((count,), np.uint8), np.zeros((count,), np.uint32)
+        total = C.c_uint64(0)
+        check(lib().tafl_pool_sample_weighted(self._h, seed, step, row_base, count, flags, *[a.ctypes.data_as(vp) for a in out], slot.ctypes.data_as(vp), sym.ctypes.data_as(vp),
+                                              weight.ctypes.data_as(vp), C.cast(C.byref(total), vp), 0))
+        return (*out, slot, sym, weight, int(total.value))
+
+    def weight_stats(self) -> TaflPoolWeightCounters:
+        """enabled, ingest_weight, total_weight, positive, bad_slot, rebuilds, device_bytes (all zero while weighting is off)."""
+        st = TaflPoolWeightCounters()
+        check(lib().tafl_pool_weight_stats(self._h, C.byref(st)))
+        return st
 
     def read(self, slots):
         """The sparse form of the rows in `slots` as numpy arrays: (n_children [k], move_no [k], generation [k], actions [k, max_children],

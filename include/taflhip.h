@@ -911,7 +911,8 @@ int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device)
  * The piece between "self-play wrote examples" and "the trainer takes a minibatch": a fixed-capacity ring of finished examples in HBM that
  * outlives the tafl_examples objects it was filled from (alpha-zero-general keeps the examples of the last N iterations and trains on
  * shuffled batches of them).  tafl_pool_ingest compacts the finished examples of an examples object into it, tafl_pool_sample draws rows
- * uniformly under random board symmetries.  Build-defined.  Nothing else in this header behaves differently.
+ * uniformly under random board symmetries, tafl_pool_sample_weighted in proportion to per-row integer weights the trainer hands back.
+ * Build-defined.  Nothing else in this header behaves differently.
  *
  * Rows and slots.  A pool has `capacity` C rows (1 <= C < 2^32) of `max_children` Kp (1..65535) policy entries.  The q-th row ever taken
  *   (q from 0) lives in slot q mod C.  live = min(written, C) minus what tafl_pool_trim removed; the live rows are those with q in
@@ -962,8 +963,41 @@ int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device)
  * tafl_pool_read: the sparse form of the rows in slot[0 .. count) (host pointers; a slot that is not live: TAFL_ERR_INVALID_ARG):
  *   n_children[i], move_no[i], generation[i], actions / visits [i * Kp + k].  Any output may be NULL.  It copies every row between the
  *   lowest and the highest slot asked for to the host: not a hot path.
- * Not offered: saving and loading a pool, weighted or prioritised sampling, sampling without replacement, de-duplication of positions,
- *   ingesting examples that are not final, a pool that spans devices. */
+ * Weighted sampling (off by default; while it is off the pool behaves and allocates as described above).  wt[s] is a uint32 per slot,
+ *     eff(s) = slot s is live ? wt[s] : 0,   W(s) = sum of eff(t) for t < s, in SLOT order, 64 bits,   total = W(C).
+ *   Slot order, not age order: the probability of a row is the same and the wrap of the window drops out of the search.  A weight left in
+ *   a slot that is no longer live counts for nothing and needs no clearing.
+ * tafl_pool_set_weighting(pool, w): w != NULL switches weighting on (flags or reserved words not 0: TAFL_ERR_UNSUPPORTED).  Off -> on
+ *   allocates 4 bytes per slot (C rounded up to a multiple of 256), 20 bytes per 256 slots and 24 bytes, and gives EVERY slot
+ *   w->ingest_weight; on -> on only changes ingest_weight for later ingests, stored weights stay.  w == NULL switches it off and frees
+ *   those buffers and the staging of the weighted calls: tafl_pool_stats.device_bytes is what it was before (apart from row staging a
+ *   weighted sample with host pointers grew, which is the staging of tafl_pool_sample).  tafl_pool_clear keeps the setting and the stored
+ *   weights (no slot is live then).  While weighting is on, every row an ingest stores (ranks r >= T - min(T, C)) gets
+ *   wt[slot] = ingest_weight.
+ * tafl_pool_set_weights(pool, slot, weight, count, ptrs_are_device): afterwards every LIVE slot s named by the call holds the MAXIMUM of
+ *   the weights the call gives for s (a sample with replacement names slots twice: the result does not depend on an order); slots not
+ *   named are unchanged.  Weight 0 is legal: such a row is never drawn.  Host pointers: a slot that is not live fails the call with
+ *   TAFL_ERR_INVALID_ARG before anything is written.  Device pointers: such an entry is skipped and counted in
+ *   tafl_pool_weight_counters.bad_slot, the kernels are enqueued on the context's stream and nothing is read back.  Weighting off:
+ *   TAFL_ERR_INVALID_ARG.  tafl_pool_get_weights reads weight[i] = wt[slot[i]]: a slot that is not live is refused with host pointers
+ *   and reported as 0 with device pointers.
+ * tafl_pool_sample_weighted: row i < count uses row = row_base + i (a sum above 32 bits: TAFL_ERR_INVALID_ARG) and
+ *     dk   = sim_key(game_key(seed, step) ^ 0x504F4F4C57445257, row)       "POOLWDRW"
+ *     r    = (uint64)ply_rand(dk, 2) << 32 | ply_rand(dk, 3)
+ *     k    = (r * total) >> 64                                             128-bit product: k < total
+ *     slot = the one s with W(s) <= k < W(s) + eff(s)
+ *     sym  = flags & TAFL_POOL_SAMPLE_SYM ? ply_rand(dk, 1) >> 29 : 0
+ *   Row i is what tafl_pool_gather writes for (slot, sym); out_slot[i], out_sym[i], out_weight[i] = wt[slot] and *out_total = total (one
+ *   uint64; each may be NULL) receive the draw: a row's probability is wt / total, which is the caller's importance correction.  Integers
+ *   only, a pure function of (seed, step, row, written, live, C, wt): ranks passing row_base = k * count draw the rows of one big call.
+ *   Weighting off, live == 0 or total == 0: TAFL_ERR_INVALID_ARG; unknown flag bits: TAFL_ERR_UNSUPPORTED.  With device pointers every
+ *   pointer (out_total too) is a device pointer.  tafl_pool_sample is untouched and ignores the weights.
+ *   The sums behind the search are rebuilt in full (4 bytes read per slot) by the first weighted sample or tafl_pool_weight_stats after
+ *   an ingest, a trim, a clear, tafl_pool_set_weights or tafl_pool_set_weighting; that rebuild reads 16 bytes back.
+ * tafl_pool_weight_stats: enabled, ingest_weight, total_weight = total, positive = live rows with a weight above 0, bad_slot, rebuilds,
+ *   device_bytes = what weighting added.  All zero while weighting is off; switching it off and tafl_pool_clear zero bad_slot and rebuilds.
+ * Not offered: saving and loading a pool, sampling without replacement, float weights, priorities computed by the library,
+ *   de-duplication of positions, ingesting examples that are not final, a pool that spans devices. */
 typedef struct tafl_pool tafl_pool;                 /* opaque, owned by the ctx's device */
 typedef struct tafl_pool_stats {
     uint64_t written;          /* rows ever taken by ingests (also those that fell out of the window) */
@@ -989,6 +1023,28 @@ int tafl_pool_gather(tafl_pool* pool, const uint32_t* slot, const uint8_t* sym, 
                      uint8_t* boards, uint8_t* sides, float* pi, float* z, int ptrs_are_device);
 int tafl_pool_read(tafl_pool* pool, const uint32_t* slot, uint32_t count, uint32_t* n_children, uint32_t* move_no,
                    uint32_t* generation, uint32_t* actions, uint32_t* visits);
+typedef struct tafl_pool_weights {
+    uint32_t ingest_weight;    /* the weight of every slot at off -> on, and of every row an ingest stores */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[6];     /* 0 */
+} tafl_pool_weights;                                /* 32 bytes */
+typedef struct tafl_pool_weight_counters {
+    uint64_t enabled;          /* 1 while weighting is on; every other field is 0 while it is off */
+    uint64_t ingest_weight;
+    uint64_t total_weight;     /* the sum of the weights of the live rows */
+    uint64_t positive;         /* live rows with a weight above 0 */
+    uint64_t bad_slot;         /* entries of device-pointer tafl_pool_set_weights calls whose slot was not live */
+    uint64_t rebuilds;         /* rebuilds of the sums behind the search */
+    uint64_t device_bytes;     /* what weighting added to tafl_pool_stats.device_bytes */
+    uint64_t _reserved;
+} tafl_pool_weight_counters;                        /* 64 bytes */
+int tafl_pool_set_weighting(tafl_pool* pool, const tafl_pool_weights* w);             /* NULL: off (the default) */
+int tafl_pool_set_weights(tafl_pool* pool, const uint32_t* slot, const uint32_t* weight, uint32_t count, int ptrs_are_device);
+int tafl_pool_get_weights(tafl_pool* pool, const uint32_t* slot, uint32_t count, uint32_t* weight, int ptrs_are_device);
+int tafl_pool_sample_weighted(tafl_pool* pool, uint64_t seed, uint64_t step, uint32_t row_base, uint32_t count, uint32_t flags,
+                              uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym,
+                              uint32_t* out_weight, uint64_t* out_total, int ptrs_are_device);
+int tafl_pool_weight_stats(tafl_pool* pool, tafl_pool_weight_counters* out);
 
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
