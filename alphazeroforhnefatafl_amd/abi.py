@@ -253,6 +253,12 @@ class TaflPoolWeightCounters(C.Structure):
                 ("bad_slot", C.c_uint64), ("rebuilds", C.c_uint64), ("device_bytes", C.c_uint64), ("_reserved", C.c_uint64)]
 
 
+class TaflPoolSurpriseWeights(C.Structure):
+    """tafl_pool_surprise_weights: the rule of tafl_pool_weights_from_surprise (base + floor(surprise * per_nat), saturating)."""
+    _fields_ = [("base", C.c_uint32), ("generation", C.c_uint32), ("per_nat", C.c_double), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
+
+
+EXAMPLES_SEARCH_STATS = 0x1      # tafl_examples_create_ex flags: keep Qsa and Ps of every stored child
 POOL_SAMPLE_SYM = 0x1            # tafl_pool_sample flags: draw one of the eight symmetries per row
 
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
@@ -262,7 +268,8 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_match_stats": 128, "tafl_playout_cap": 32, "tafl_playout_cap_stats": 32,
                   "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
                   "tafl_eval_symmetry": 32,
-                  "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32, "tafl_pool_weights": 32, "tafl_pool_weight_counters": 64}
+                  "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32, "tafl_pool_weights": 32, "tafl_pool_weight_counters": 64,
+                  "tafl_pool_surprise_weights": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -274,7 +281,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_forced_playouts", TaflForcedPlayouts), ("tafl_forced_playouts_stats", TaflForcedPlayoutsStats),
                     ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats), ("tafl_eval_symmetry", TaflEvalSymmetry),
                     ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult),
-                    ("tafl_pool_weights", TaflPoolWeights), ("tafl_pool_weight_counters", TaflPoolWeightCounters)]:
+                    ("tafl_pool_weights", TaflPoolWeights), ("tafl_pool_weight_counters", TaflPoolWeightCounters),
+                    ("tafl_pool_surprise_weights", TaflPoolSurpriseWeights)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

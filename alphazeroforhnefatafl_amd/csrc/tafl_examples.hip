@@ -59,11 +59,29 @@ __global__ __launch_bounds__(256) void k_examples_gather(ExamplesMem X, const ui
     }
 }
 
+// The two scalars of tafl_examples_gather_stats, one lane per row: value[i], surprise[i] of example index[i] (example_search_stats); an
+// index that names no example gives zeros and is counted
+__global__ __launch_bounds__(256) void k_examples_gather_stats(ExamplesMem X, ExampleStatsMem S, const uint32_t* index, uint32_t count, float* value, float* surprise) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t e = index[i], g = e % X.G, j = e / X.G;
+    const bool ok = j < X.max_moves && j < X.len[g];
+    float v = 0.0f, s = 0.0f;
+    if (ok) example_search_stats(X, S, j, g, X.info[e], v, s);
+    else atomicAdd(&X.counters[EX_BAD_INDEX], 1ull);
+    if (value) value[i] = v;
+    if (surprise) surprise[i] = s;
+}
+
 #define EXCHK(ex, name) do { if (!(ex)) return fail(TAFL_ERR_INVALID_ARG, name ": null examples object"); HIPCHK(hipSetDevice((ex)->ctx->device)); } while (0)
 
 extern "C" {
 
 int tafl_examples_create(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint32_t max_children, tafl_examples** out) {
+    return tafl_examples_create_ex(c, n_games, max_moves, max_children, 0u, out);
+}
+int tafl_examples_create_ex(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint32_t max_children, uint32_t flags, tafl_examples** out) {
+    if (flags & ~(uint32_t)TAFL_EXAMPLES_SEARCH_STATS) return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_create_ex: unknown flag bits");
     if (!c || !out || n_games == 0 || max_moves == 0 || max_children == 0 || max_children > 0xFFFFu)
         return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: bad argument (n_games, max_moves >= 1, max_children in 1..65535)");
     if ((unsigned long long)n_games * max_moves > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: n_games * max_moves exceeds 32 bits");
@@ -71,17 +89,19 @@ int tafl_examples_create(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint
     tafl_examples* x = new (std::nothrow) tafl_examples();
     if (!x) return fail(TAFL_ERR_OOM, "out of host memory");
     c->live_batches += 1;                                    // (the context outlives its examples objects as it outlives its batches)
-    x->ctx = c; x->n_games = n_games; x->max_moves = max_moves; x->max_children = max_children;
+    x->ctx = c; x->n_games = n_games; x->max_moves = max_moves; x->max_children = max_children; x->flags = flags;
     const size_t E = (size_t)n_games * max_moves, BW = ((size_t)c->n * c->n + 3) / 4;
     if (x->need(x->len, 4 * (size_t)n_games) || x->need(x->boards, 4 * E * BW) || x->need(x->info, 4 * E) || x->need(x->played, 4 * E) || x->need(x->move_no, 4 * E) ||
         x->need(x->pol, 4 * E * max_children) || x->need(x->z, 4 * E) || x->need(x->fin, E) || x->need(x->counters, 8 * EX_COUNTERS) ||
-        x->need(x->open_from, 4 * (size_t)n_games)) {
+        x->need(x->open_from, 4 * (size_t)n_games) ||
+        ((flags & TAFL_EXAMPLES_SEARCH_STATS) && (x->need(x->cq, 4 * E * max_children) || x->need(x->cp, 4 * E * max_children) || x->need(x->seen, 4 * (size_t)n_games)))) {
         tafl_examples_destroy(x);
         return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_examples_create)");
     }
     ExamplesMem& M = x->mem;
     x->len.bind(M.len); x->boards.bind(M.boards); x->info.bind(M.info); x->played.bind(M.played); x->move_no.bind(M.move_no);
     x->pol.bind(M.pol); x->z.bind(M.z); x->fin.bind(M.fin); x->counters.bind(M.counters);
+    if (flags & TAFL_EXAMPLES_SEARCH_STATS) { x->cq.bind(x->smem.cq); x->cp.bind(x->smem.cp); x->seen.bind(x->smem.seen); }
     M.G = n_games; M.max_moves = max_moves; M.K = max_children; M.BW = (uint32_t)BW;
     const int rc = tafl_examples_clear(x);
     if (rc) { tafl_examples_destroy(x); return rc; }
@@ -102,6 +122,7 @@ int tafl_examples_clear(tafl_examples* x) {
     HIPCHK(hipMemsetAsync(x->len.p, 0, 4 * (size_t)x->n_games, s));
     HIPCHK(hipMemsetAsync(x->counters.p, 0, 8 * EX_COUNTERS, s));
     HIPCHK(hipMemsetAsync(x->open_from.p, 0, 4 * (size_t)x->n_games, s));
+    if (x->seen.p) HIPCHK(hipMemsetAsync(x->seen.p, 0, 4 * (size_t)x->n_games, s));
     return sync_ok(x->ctx);
 }
 int tafl_examples_counts(tafl_examples* x, uint32_t* out_len, uint64_t* out_total) {
@@ -139,6 +160,7 @@ int tafl_selfplay_record(tafl_batch* b, const tafl_mcts_params* p, const tafl_se
     if (!b) return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: null batch");
     if (ex && (ex->n_games != b->n || ex->ctx->device != b->ctx->device || ex->ctx->n != b->ctx->n))
         return fail(TAFL_ERR_INVALID_ARG, "tafl_selfplay_record: the examples object was created for another batch size, board or device");
+    if (ex && (ex->flags & TAFL_EXAMPLES_SEARCH_STATS)) return fail(TAFL_ERR_UNSUPPORTED, "tafl_selfplay_record: the examples object carries search statistics (TAFL_EXAMPLES_SEARCH_STATS), which a rollout-mode search has none of");
     SelfPlayRec rec{};
     if (ex) rec.ex = ex->mem;
     rec.sample_seed = o->sample_seed; rec.game_id_base = game_id_base; rec.temp_moves = o->temp_moves; rec.move_base = o->move_base;
@@ -198,6 +220,39 @@ int tafl_examples_read(tafl_examples* x, const uint32_t* index, uint32_t count, 
     return TAFL_OK;
 }
 
+// Qsa and Ps of the stored children (TAFL_EXAMPLES_SEARCH_STATS), the slow path beside tafl_examples_read: host pointers, [count * K]
+int tafl_examples_read_stats(tafl_examples* x, const uint32_t* index, uint32_t count, float* q, float* prior) {
+    EXCHK(x, "tafl_examples_read_stats");
+    if (!(x->flags & TAFL_EXAMPLES_SEARCH_STATS)) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read_stats: the object was created without TAFL_EXAMPLES_SEARCH_STATS");
+    if (!index && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read_stats: null index");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = x->ctx->stream;
+    const size_t K = x->max_children, G = x->n_games;
+    size_t jmax = 0;
+    for (uint32_t i = 0; i < count; ++i) {
+        const size_t j = index[i] / G;
+        if (j >= x->max_moves) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read_stats: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        if (j > jmax) jmax = j;
+    }
+    const size_t E = (jmax + 1) * G;
+    std::vector<uint32_t> len(G), info(E); std::vector<float> hq(q ? E * K : 0), hp(prior ? E * K : 0);
+    COPY_OUT(len.data(), x->len.p, G, s);
+    COPY_OUT(info.data(), x->info.p, E, s);
+    if (q) COPY_OUT(hq.data(), x->cq.p, E * K, s);
+    if (prior) COPY_OUT(hp.data(), x->cp.p, E * K, s);
+    HIPCHK(hipStreamSynchronize(s));
+    for (uint32_t i = 0; i < count; ++i) {
+        const size_t e = index[i], g = e % G, j = e / G;
+        if (j >= len[g]) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_read_stats: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        const uint32_t nc = example_stored_children(x->mem, info[e]);
+        for (size_t k = 0; k < K; ++k) {
+            if (q) q[(size_t)i * K + k] = k < nc ? hq[(j * K + k) * G + g] : 0.0f;
+            if (prior) prior[(size_t)i * K + k] = k < nc ? hp[(j * K + k) * G + g] : 0.0f;
+        }
+    }
+    return TAFL_OK;
+}
+
 static int examples_gather_launch(tafl_examples* x, const uint32_t* index, const uint8_t* sym, uint32_t count, uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* fin) {
     tafl_ctx* c = x->ctx;
     const uint32_t A = c->n * c->n * 2u * (c->n - 1u);
@@ -246,6 +301,38 @@ int tafl_examples_gather(tafl_examples* x, const uint32_t* index, const uint8_t*
         if (final_) COPY_OUT(final_ + i0, x->g_fin.p, k, s);
         HIPCHK(hipStreamSynchronize(s));
     }
+    return TAFL_OK;
+}
+
+// value and surprise per row (example_search_stats): with device pointers one asynchronous launch, a bad index gives zeros and is counted
+int tafl_examples_gather_stats(tafl_examples* x, const uint32_t* index, uint32_t count, float* value, float* surprise, int ptrs_are_device) {
+    EXCHK(x, "tafl_examples_gather_stats");
+    if (!(x->flags & TAFL_EXAMPLES_SEARCH_STATS)) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_stats: the object was created without TAFL_EXAMPLES_SEARCH_STATS");
+    if (!index && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_stats: null index");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = x->ctx->stream;
+    const uint32_t grid = (uint32_t)(((unsigned long long)count + 255u) / 256u);
+    if (ptrs_are_device) {
+        hipLaunchKernelGGL(k_examples_gather_stats, dim3(grid), dim3(256), 0, s, x->mem, x->smem, index, count, value, surprise);
+        HIPCHK(hipGetLastError());
+        return TAFL_OK;
+    }
+    {
+        std::vector<uint32_t> len(x->n_games);
+        COPY_OUT(len.data(), x->len.p, x->n_games, s);
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t g = index[i] % x->n_games, j = index[i] / x->n_games;
+            if (j >= x->max_moves || j >= len[g]) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_stats: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        }
+    }
+    EXNEED(x->g_index, 4 * (size_t)count); EXNEED(x->g_z, 4 * (size_t)count); EXNEED(x->g_s, 4 * (size_t)count);
+    HIPCHK(hipMemcpyAsync(x->g_index.p, index, 4 * (size_t)count, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_examples_gather_stats, dim3(grid), dim3(256), 0, s, x->mem, x->smem, x->g_index.as<const uint32_t>(), count, x->g_z.as<float>(), x->g_s.as<float>());
+    HIPCHK(hipGetLastError());
+    COPY_OUT(value, x->g_z.p, count, s);
+    COPY_OUT(surprise, x->g_s.p, count, s);
+    HIPCHK(hipStreamSynchronize(s));
     return TAFL_OK;
 }
 

@@ -6,6 +6,7 @@
 // and so is the draw of a play in proportion to the visit counts (visit_draw).  __host__ __device__ like everything in tafl_ops.hpp: the
 // kernels run these functions one game (or one example, or one tile) per lane, tests/hostsim runs the same code on the CPU.
 #pragma once
+#include <math.h>
 #include "tafl_core.hpp"
 
 #define TAFL_DRAW_VALUE 1e-4     /* getGameEnded draw convention, DESIGN.md: the value of a drawn terminal in the search and z of a drawn game */
@@ -32,6 +33,14 @@ struct ExamplesMem {
     uint8_t* fin;                // [e] 1: z is final
     unsigned long long* counters;   // [EX_COUNTERS]
     uint32_t G, max_moves, K, BW;
+};
+// Search statistics per stored child (include/taflhip.h TAFL_EXAMPLES_SEARCH_STATS), of an object created with the
+// flag.  A struct of its own and not a part of ExamplesMem: the self-play rounds take ExamplesMem by value and stay what they were; only
+// the recorder kernel that runs after a guided round (Guided::record_stats) and the readers below take this one.
+struct ExampleStatsMem {
+    float* cq;                   // [(j * K + k) * G + g] Qsa of the k-th stored child, laid out like pol
+    float* cp;                   // [(j * K + k) * G + g] Ps of the k-th stored child as the root's edges held it
+    uint32_t* seen;              // [G] examples of game g the recorder has dealt with (a run sets it to len at its begin)
 };
 // what a recording run adds to SelfPlay: ex.len == nullptr records nothing (the plays are still drawn)
 struct SelfPlayRec {
@@ -74,6 +83,33 @@ static TAFL_HD void example_append(const ExamplesMem& X, uint32_t g, const DStat
     X.info[e] = (over ? kExOverflow : m) | (((st.flags & TAFL_F_SIDE) ? (uint32_t)TAFL_DEFENDER : (uint32_t)TAFL_ATTACKER) << 16);
     X.played[e] = played | (total << 16); X.move_no[e] = move_no; X.z[e] = 0.0f; X.fin[e] = 0;
     X.len[g] = j + 1u;
+}
+
+// The two scalars a training row derives from its stored children (include/taflhip.h "search value and policy surprise"; the text there
+// is normative).  Both are 0 for an example without a stored policy (overflowed, or no children).
+//   value     N = sum Nsa; acc = 0; for k ascending: acc = acc + (double)Nsa_k * (double)cq_k; value = (float)(acc / (double)N)
+//   surprise  pi_k = (double)Nsa_k / (double)N; s = sum_k pi_k * (log(pi_k) - log(max((double)cp_k, 2^-126))), ascending, in double;
+//             surprise = (float)max(s, 0.0): KL(pi || P) over the stored children
+// `info` is the example's info word.  No FMA contraction on either build, so value is the same bits on the host and on the device.
+static TAFL_HD uint32_t example_stored_children(const ExamplesMem& X, uint32_t info) {
+    const uint32_t nc = (info & kExOverflow) ? 0u : (info & 0xFFFFu);
+    return nc <= X.K ? nc : 0u;
+}
+static TAFL_HD void example_search_stats(const ExamplesMem& X, const ExampleStatsMem& S, uint32_t j, uint32_t g, uint32_t info, float& value, float& surprise) {
+    const uint32_t nc = example_stored_children(X, info);
+    value = 0.0f; surprise = 0.0f;
+    uint32_t N = 0;
+    for (uint32_t k = 0; k < nc; ++k) N += X.pol[((size_t)j * X.K + k) * X.G + g] >> 16;
+    if (N == 0u) return;
+    double acc = 0.0, s = 0.0;
+    for (uint32_t k = 0; k < nc; ++k) {
+        const size_t at = ((size_t)j * X.K + k) * X.G + g;
+        const double v = (double)(X.pol[at] >> 16), pi = v / (double)N, pr = (double)S.cp[at];
+        acc = acc + v * (double)S.cq[at];
+        s = s + pi * (log(pi) - log(pr > 0x1p-126 ? pr : 0x1p-126));
+    }
+    value = (float)(acc / (double)N);
+    surprise = (float)(s > 0.0 ? s : 0.0);
 }
 
 // The entry a move is drawn with, among n entries of which entry j has count(j) visits: k = mulhi(r, N) = (r * N) >> 32 with N = the sum of

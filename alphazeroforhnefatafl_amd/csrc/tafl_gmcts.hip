@@ -721,7 +721,25 @@ int tafl_gmcts_get_stats(tafl_batch* b, tafl_gmcts_stats* out) {
 }
 
 // ---- guided self-play at each game's own pace -----------------------------------------------------------------
+// the recorder of search statistics (Guided record_stats): one lane per game, after the round and its reopen, on
+// the same stream; launched only for a run whose examples object carries the arrays
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_record_stats(GuidedMem M, ExamplesMem X, ExampleStatsMem S) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= M.G) return;
+    record_stats(M, g, X, S);
+}
+static int gselfplay_record_stats(tafl_batch* b) {
+    if (!b->gsp_stats.cq) return TAFL_OK;
+    LAUNCH_PER_GAME(k_gselfplay_record_stats, b->ctx, b->n, b->gmem, b->gsp_rec.ex, b->gsp_stats);
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
+static int gselfplay_rounds(tafl_batch* b, const float* dp, const float* dv);
 static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
+    if (const int rc = gselfplay_rounds(b, dp, dv)) return rc;
+    return gselfplay_record_stats(b);
+}
+static int gselfplay_rounds(tafl_batch* b, const float* dp, const float* dv) {
     tafl_ctx* c = b->ctx; const uint32_t n = b->n, A = tafl_action_size(c);
     unsigned long long* st = b->g_stats.as<unsigned long long>();
     HIPCHK(hipMemsetAsync(st + GS_WAITING, 0, sizeof(unsigned long long), c->stream));
@@ -819,6 +837,11 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
     }
     b->gsp_rec = SelfPlayRec{};
     if (ex) b->gsp_rec.ex = ex->mem;
+    b->gsp_stats = ExampleStatsMem{};
+    if (ex && (ex->flags & TAFL_EXAMPLES_SEARCH_STATS)) {      // the recorder deals with what this run appends: seen = len
+        b->gsp_stats = ex->smem;
+        HIPCHK(hipMemcpyAsync(ex->seen.p, ex->len.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
+    }
     b->gsp_rec.sample_seed = o->sample_seed; b->gsp_rec.game_id_base = game_id_base; b->gsp_rec.temp_moves = o->temp_moves; b->gsp_rec.move_base = o->move_base;
     b->gsp_sims = n_sims; b->gsp_cpuct = c_puct;
     b->g_noise_on = b->noise_set;                            // the run latches the noise setting; gid and M are the run's own
@@ -1010,6 +1033,7 @@ int tafl_gmatch_step(tafl_batch* b, const float* const priors[2], const float* c
     HIPCHK(hipGetLastError());
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_gselfplay_reopen<t.NL, t.W>), c, n, b->gmem, b->soa, b->gsp, b->gsp_ep, b->gsp_rec, st); });
     HIPCHK(hipGetLastError());
+    if (const int rc = gselfplay_record_stats(b)) return rc;
     return in_is_device ? TAFL_OK : sync_ok(c);                // (host arrays may be reused once the call returns)
 }
 

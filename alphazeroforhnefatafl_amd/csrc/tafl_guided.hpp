@@ -176,6 +176,32 @@ static TAFL_HD double noise_gamma(const RootNoise& nz, uint32_t a) {
 // eta_i from gamma_i, the sequential sum s of the root's variates and the number n of its legal actions
 static TAFL_HD double noise_eta(double gamma, double s, uint32_t n) { return (s > 0.0 && s < __builtin_inf()) ? gamma / s : 1.0 / (double)n; }
 
+// The recorder of search statistics (tafl_examples.hpp ExampleStatsMem), for game g AFTER a self-play round of any family: if the round
+// appended an example (len[g] has passed seen[g]; a round appends at most one, a move needs its root's evaluation) that holds a policy,
+// Qsa and Ps of its stored children are read from the block of the root the move was made from.  That block still stands: init_game resets
+// edge_top and writes no edge, the block begins at edge 0 of the game's arena (the root is the first node a search expands) and the next
+// expansion needs an evaluation, hence a later round.  The stored actions ascend and each is in the block, so child k's edge is the next
+// one with its action; the pruning rounds edit n in that block in place and leave q and p.  The walk never leaves the game's arena: it
+// is bounded by edge_cap and not by the root's n_legal, which init_game has overwritten - an action that were not in the block (none is)
+// would be looked for among the stale edges behind it and, not found, store zeros.
+static TAFL_HD void record_stats(const GuidedMem& M, uint32_t g, const ExamplesMem& X, const ExampleStatsMem& S) {
+    const uint32_t len = X.len[g] < X.max_moves ? X.len[g] : X.max_moves, seen = S.seen[g];
+    if (len == seen) return;
+    S.seen[g] = len;
+    if (len < seen) return;                                      // (the object was cleared under the run)
+    const uint32_t j = len - 1u, info = X.info[(size_t)j * X.G + g], nc = example_stored_children(X, info);
+    const GEdge* eb = &M.edges[(size_t)g * M.edge_cap];
+    uint32_t i = 0;
+    for (uint32_t k = 0; k < nc; ++k) {
+        const size_t at = ((size_t)j * X.K + k) * X.G + g;
+        const uint32_t a = X.pol[at] & 0xFFFFu;
+        while (i < M.edge_cap && eb[i].action != a) ++i;
+        float q = 0.0f, p = 0.0f;
+        if (i < M.edge_cap) { q = (float)eb[i].q; p = (float)eb[i].p; ++i; }
+        S.cq[at] = q; S.cp[at] = p;
+    }
+}
+
 template <int NL, int W>
 struct Guided {
     using E = Engine<NL, W>;
@@ -184,6 +210,7 @@ struct Guided {
     using K = Consts<NL>;
     using IO = StateIO<NL>;
 
+    // (writes no edge: record_stats above reads the block of the root a move was just made from AFTER this has run for the next root)
     static TAFL_HD void init_game(const GuidedMem& M, uint32_t g, const S& root) {
         GNode h; h.parent = 0; h.edge_base = 0; h.ns = 0; h.n_legal = 0; h.term = O::term_code(root); h.expanded = 0;
         M.hdr[g] = h; M.pedge[g] = 0;
@@ -639,7 +666,9 @@ struct Guided {
             full = cap_is_full(*pc, gid, EPISODES ? md - m0 : rec.move_base + md);
             if (!full && M.kind[g] == 1 && M.leaf[g] == 0u) M.sims_done[g] = n_sims - pc->fast_sims;      // (fast_sims <= n_sims: the begin checks it)
         }
-        // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root)
+        // (a loop so that `step` is inlined once: its second pass is the first round of the next search and ends at the unexpanded root;
+        // record_stats depends on that: no expansion, hence no edge write, between a move and the end of the round.  Subtree reuse in a
+        // run, or a search that expands before its evaluation, would have to record before it overwrites the block)
         for (;;) {
             if constexpr (SOLVER) {
                 uint32_t forced = 0, sl[SL_COUNT] = {0u, 0u, 0u};

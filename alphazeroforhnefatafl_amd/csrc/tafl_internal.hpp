@@ -225,6 +225,7 @@ struct tafl_batch {
     // the first round and the first tafl_gselfplay_step reports it; gsp_has: the buffers hold the plays of a run (tafl_gselfplay_end)
     bool gsp_active = false, gsp_first = false, gsp_has = false;
     GSelfPlay gsp = {}; SelfPlayRec gsp_rec = {}; uint32_t gsp_sims = 0; double gsp_cpuct = 0.0;
+    ExampleStatsMem gsp_stats = {};  // the run records into an examples object with search statistics (cq != nullptr): k_gselfplay_record_stats follows every round
     DevBuf gsp_moves_done, gsp_plays;
     // an episodes run (tafl_gselfplay_begin_episodes): per lane the episode number and the move count at which it began, the openings
     // (quad-plane SoA like the batch states) and the four result counters; gsp_episodes: the run that is open, or was last, is one
@@ -268,8 +269,11 @@ struct tafl_batch {
 struct tafl_examples {
     tafl_ctx* ctx;
     uint32_t n_games, max_moves, max_children;
+    uint32_t flags = 0;              // TAFL_EXAMPLES_* of tafl_examples_create_ex
     ExamplesMem mem;
+    ExampleStatsMem smem = {};       // TAFL_EXAMPLES_SEARCH_STATS: the arrays beside pol (all null without the flag)
     DevBuf len, boards, info, played, move_no, pol, z, fin, counters;
+    DevBuf cq, cp, seen, g_s;        // g_s: staging of the second scalar of a host-pointer tafl_examples_gather_stats
     DevBuf open_from;                // [n_games] first example of game g whose result is still open: 0 unless an episodes run has moved it
     DevBuf g_index, g_sym, g_boards, g_sides, g_pi, g_z, g_fin;      // staging of a gather with host pointers
     size_t device_bytes = 0;         // sum of the capacities above: every allocation goes through need()

@@ -100,6 +100,45 @@ __global__ __launch_bounds__(POOL_TILE) void k_pool_copy(ExamplesMem X, uint32_t
     }
 }
 
+// Ingest, the pass of a pool that carries search statistics (tafl_pool_set_search_stats): one lane per example in the order of the
+// per-example arrays, so that a wave reads consecutive g; the rank comes from the prefix k_pool_copy used, through pool_tile_flags, and the
+// two scalars of a stored example (example_search_stats, the functions of tafl_examples_gather_stats) go to its slot.  What the copy
+// skips - the ranks below T - min(T, C) - is skipped here.
+__global__ __launch_bounds__(POOL_TILE) void k_pool_ingest_stats(ExamplesMem X, ExampleStatsMem S, uint32_t E, const uint32_t* prefix, const unsigned long long* res,
+                                                                 unsigned long long written, uint32_t C, float* value, float* surprise) {
+    __shared__ uint32_t wave_tot[POOL_TILE / 64];
+    uint32_t info, e, lr, nt;
+    const bool taken = pool_tile_flags(X, E, wave_tot, info, e, lr, nt) == POOL_TAKEN;
+    if (!taken) return;
+    const uint32_t T = (uint32_t)res[0], rank = prefix[blockIdx.x] + lr, first = T - (T < C ? T : C);
+    if (rank < first) return;
+    float v, s;
+    example_search_stats(X, S, e / X.G, e % X.G, info, v, s);
+    const uint32_t slot = pool_stored_slot(written, rank - first, T, C);
+    value[slot] = v; surprise[slot] = s;
+}
+// tafl_pool_gather_stats: zeros for a slot that is not live, counted
+__global__ __launch_bounds__(256) void k_pool_gather_stats(const float* sv, const float* ss, unsigned long long* counters, const uint32_t* slot, uint32_t count, uint32_t first,
+                                                           unsigned long long live, uint32_t C, float* value, float* surprise) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        const bool ok = pool_slot_live_from(s, first, live, C);
+        if (!ok) atomicAdd(&counters[POOL_BAD_SLOT], 1ull);
+        if (value) value[i] = ok ? sv[s] : 0.0f;
+        if (surprise) surprise[i] = ok ? ss[s] : 0.0f;
+    }
+}
+// tafl_pool_weights_from_surprise: every live slot whose row has the generation (0: every live slot) is ASSIGNED pool_surprise_weight
+__global__ __launch_bounds__(256) void k_poolw_from_surprise(uint32_t* wt, const float* ss, const uint32_t* rows, uint32_t RW, uint32_t gen_word, uint32_t first, unsigned long long live,
+                                                             uint32_t C, uint32_t base, uint32_t generation, double per_nat) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < C; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = (uint32_t)i;
+        if (!pool_slot_live_from(s, first, live, C)) continue;
+        if (generation != 0u && rows[(size_t)s * RW + gen_word] != generation) continue;
+        wt[s] = pool_surprise_weight(ss[s], base, per_nat);
+    }
+}
+
 // Minibatch rows (tafl_pool_sample: DRAW, tafl_pool_gather: slot_in / sym_in): row i = the row of a slot under a symmetry, in the shape
 // of k_examples_gather - the dense policy row is built in LDS, which is all zero between two rows, and streamed out with full-width
 // stores - reading one contiguous row.  One workgroup serves rows blockIdx.x, blockIdx.x + gridDim.x, ...
@@ -271,6 +310,9 @@ struct tafl_pool {
         for (DevBuf* d : {&wt, &wtiles, &wres, &w_slot, &w_sym, &w_weight}) { device_bytes -= d->cap; d->release(); }
         weight_bytes = 0; weighting = false; wmem = PoolWeights{};
     }
+    // search statistics per row (tafl_pool_set_search_stats; off: no buffer of it exists): value and surprise of the row in slot s
+    bool search_stats = false;
+    DevBuf s_value, s_surprise, g_s;     // g_s: staging of the second scalar of a host-pointer tafl_pool_gather_stats
     uint32_t first_live() const { return book.live ? pool_first_live(book.written, book.live, mem.C) : 0u; }
 };
 
@@ -381,6 +423,8 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     if (ex->ctx != p->ctx) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the examples object belongs to another context (board size or device)");
     if (ex->max_children > p->mem.Kp) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the examples hold more policy entries (max_children) than a row of the pool");
     if (p->book.ingests >= 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the generation exceeds 32 bits");
+    if (p->search_stats && !(ex->flags & TAFL_EXAMPLES_SEARCH_STATS))
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the pool carries search statistics, the examples object was created without TAFL_EXAMPLES_SEARCH_STATS");
     tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
     const uint32_t E = ex->n_games * ex->max_moves, nb = (uint32_t)(((unsigned long long)E + POOL_TILE - 1) / POOL_TILE);       // (E fits 32 bits: tafl_examples_create)
     POOLNEED(p->blk, 16 * (size_t)nb);
@@ -391,6 +435,9 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     hipLaunchKernelGGL(k_pool_scan, dim3(1), dim3(POOL_TILE), 0, s, (const uint32_t*)taken, (const uint32_t*)open, (const uint32_t*)over, nb, prefix, res);
     hipLaunchKernelGGL(k_pool_copy, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, E, p->mem, (const uint32_t*)prefix, (const unsigned long long*)res,
                        (unsigned long long)p->book.written, generation);
+    if (p->search_stats)
+        hipLaunchKernelGGL(k_pool_ingest_stats, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, ex->smem, E, (const uint32_t*)prefix, (const unsigned long long*)res,
+                           (unsigned long long)p->book.written, p->mem.C, p->s_value.as<float>(), p->s_surprise.as<float>());
     if (p->weighting) {
         const uint32_t most = E < p->mem.C ? E : p->mem.C, grid = std::min<uint32_t>((most + 255u) / 256u, 2048u);       // (T <= E rows at most)
         if (grid) hipLaunchKernelGGL(k_poolw_ingest, dim3(grid), dim3(256), 0, s, p->wmem.wt, (const unsigned long long*)res, (unsigned long long)p->book.written, p->mem.C, p->ingest_weight);
@@ -617,6 +664,63 @@ int tafl_pool_sample_weighted(tafl_pool* p, uint64_t seed, uint64_t step, uint32
         if (out_weight) COPY_OUT(out_weight + i0, d_weight, k, s);
         HIPCHK(hipStreamSynchronize(s));
     }
+    return TAFL_OK;
+}
+
+int tafl_pool_set_search_stats(tafl_pool* p, int on) {
+    POOLCHK(p, "tafl_pool_set_search_stats");
+    if (p->book.live != 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_set_search_stats: the pool holds live rows (the setting changes only while live == 0)");
+    hipStream_t s = p->ctx->stream;
+    if (!on) {
+        HIPCHK(hipStreamSynchronize(s));
+        for (DevBuf* d : {&p->s_value, &p->s_surprise, &p->g_s}) { p->device_bytes -= d->cap; d->release(); }
+        p->search_stats = false;
+        return TAFL_OK;
+    }
+    if (p->search_stats) return TAFL_OK;
+    if (p->need(p->s_value, 4 * (size_t)p->mem.C) || p->need(p->s_surprise, 4 * (size_t)p->mem.C)) {
+        for (DevBuf* d : {&p->s_value, &p->s_surprise}) { p->device_bytes -= d->cap; d->release(); }
+        return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_pool_set_search_stats)");
+    }
+    HIPCHK(hipMemsetAsync(p->s_value.p, 0, 4 * (size_t)p->mem.C, s));
+    HIPCHK(hipMemsetAsync(p->s_surprise.p, 0, 4 * (size_t)p->mem.C, s));
+    p->search_stats = true;
+    return sync_ok(p->ctx);
+}
+
+int tafl_pool_gather_stats(tafl_pool* p, const uint32_t* slot, uint32_t count, float* value, float* surprise, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_gather_stats");
+    if (!p->search_stats) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_stats: search statistics are off (tafl_pool_set_search_stats)");
+    if (!slot && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_stats: null slot");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = p->ctx->stream;
+    float* dv = value; float* ds = surprise;
+    if (!ptrs_are_device) {
+        for (uint32_t i = 0; i < count; ++i)
+            if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_stats: slot " + std::to_string(slot[i]) + " (row " + std::to_string(i) + ") is not live");
+        POOLNEED(p->g_slot, 4 * (size_t)count); POOLNEED(p->g_z, 4 * (size_t)count); POOLNEED(p->g_s, 4 * (size_t)count);
+        HIPCHK(hipMemcpyAsync(p->g_slot.p, slot, 4 * (size_t)count, hipMemcpyHostToDevice, s));
+        slot = p->g_slot.as<const uint32_t>(); dv = p->g_z.as<float>(); ds = p->g_s.as<float>();
+    }
+    hipLaunchKernelGGL(k_pool_gather_stats, dim3(poolw_grid(count)), dim3(256), 0, s, p->s_value.as<const float>(), p->s_surprise.as<const float>(), p->mem.counters, slot, count,
+                       p->first_live(), (unsigned long long)p->book.live, p->mem.C, dv, ds);
+    HIPCHK(hipGetLastError());
+    if (!ptrs_are_device) { COPY_OUT(value, dv, count, s); COPY_OUT(surprise, ds, count, s); HIPCHK(hipStreamSynchronize(s)); }
+    return TAFL_OK;
+}
+
+int tafl_pool_weights_from_surprise(tafl_pool* p, const tafl_pool_surprise_weights* cfg) {
+    POOLCHK(p, "tafl_pool_weights_from_surprise");
+    if (!cfg) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_surprise: null argument");
+    if (!p->weighting || !p->search_stats) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_surprise: needs weighting (tafl_pool_set_weighting) and search statistics (tafl_pool_set_search_stats) on");
+    if (!(cfg->per_nat >= 0.0)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_surprise: per_nat must be a number >= 0");
+    if (cfg->flags) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_weights_from_surprise: flags must be 0");
+    for (uint32_t r : cfg->_reserved) if (r) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_weights_from_surprise: reserved words must be 0");
+    p->dirty = true;
+    if (p->book.live == 0) return TAFL_OK;
+    hipLaunchKernelGGL(k_poolw_from_surprise, dim3(poolw_grid(p->mem.C)), dim3(256), 0, p->ctx->stream, p->wmem.wt, p->s_surprise.as<const float>(), (const uint32_t*)p->mem.rows, p->mem.RW,
+                       p->mem.BW + (uint32_t)PR_GENERATION, p->first_live(), (unsigned long long)p->book.live, p->mem.C, cfg->base, cfg->generation, cfg->per_nat);
+    HIPCHK(hipGetLastError());
     return TAFL_OK;
 }
 

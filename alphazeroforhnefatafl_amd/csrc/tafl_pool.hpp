@@ -154,7 +154,13 @@ static TAFL_HD uint32_t pool_wpick(uint32_t e0, uint32_t e1, uint32_t e2, uint32
 }
 // the slot the rank i < min(T, C) of the rows an ingest of T taken examples stores goes to (the ranks r >= T - min(T, C), pool_place)
 static TAFL_HD uint32_t pool_stored_slot(uint64_t written, uint32_t i, uint32_t T, uint32_t C) { return (uint32_t)((written + (T - (T < C ? T : C)) + i) % C); }
-
+// the weight tafl_pool_weights_from_surprise assigns to a row of surprise `surprise`: x = (double)surprise * per_nat,
+// min(2^32 - 1, base + (x < 2^32 ? (uint64)x : 2^32 - 1))
+static TAFL_HD uint32_t pool_surprise_weight(float surprise, uint32_t base, double per_nat) {
+    const double x = (double)surprise * per_nat;
+    const uint64_t add = x < 4294967296.0 ? (uint64_t)x : 0xFFFFFFFFull, w = (uint64_t)base + add;
+    return w < 0xFFFFFFFFull ? (uint32_t)w : 0xFFFFFFFFu;
+}
 
 // The host's bookkeeping of a pool (tafl_pool_ingest, tafl_pool_trim, tafl_pool_get_stats): the live rows are [written - live, written),
 // and per ingest that may still have a live row, the row number its rows end before.  Rows are in age order and generations are

@@ -73,15 +73,20 @@ class BatchedGameLogic:
             b.reset_fen(fen, self.rules.starting_side if side_to_play is None else side_to_play)
         return b
 
-    def new_examples(self, n_games: int, max_moves: int, max_children: int) -> "Examples":
+    def new_examples(self, n_games: int, max_moves: int, max_children: int, search_stats: bool = False) -> "Examples":
         """A device-resident buffer of training examples for batches of `n_games` games: room for `max_moves` examples per game with up
-        to `max_children` policy entries each (max_children >= n_sims can never overflow).  Filled by GameBatch.selfplay_record."""
-        return Examples(self, n_games, max_moves, max_children)
+        to `max_children` policy entries each (max_children >= n_sims can never overflow).  Filled by GameBatch.selfplay_record.
+        search_stats: guided self-play runs also keep Qsa and the prior of every stored child (Examples.read_stats, .gather_stats);
+        rollout-mode recording refuses such an object."""
+        return Examples(self, n_games, max_moves, max_children, search_stats)
 
-    def new_pool(self, capacity: int, max_children: int) -> "Pool":
+    def new_pool(self, capacity: int, max_children: int, search_stats: bool = False) -> "Pool":
         """A training pool on the device: a ring of `capacity` finished examples with up to `max_children` policy entries each, filled by
-        Pool.ingest from Examples objects and sampled by Pool.sample (tafl_pool_*)."""
-        return Pool(self, capacity, max_children)
+        Pool.ingest from Examples objects and sampled by Pool.sample (tafl_pool_*).  search_stats: Pool.set_search_stats(True)."""
+        p = Pool(self, capacity, max_children)
+        if search_stats:
+            p.set_search_stats(True)
+        return p
 
     def state_from_fen(self, fen: str, side_to_play: int | None = None) -> TaflState:
         st = TaflState()
@@ -604,11 +609,12 @@ class Examples:
     """Training examples (board, side to move, sparse search policy, play, result z) in HBM (tafl_examples).  Example j of game g has the
     index j * n_games + g.  The object outlives runs and batches: an episode may be recorded in several runs, a trainer may keep several."""
 
-    def __init__(self, logic: BatchedGameLogic, n_games: int, max_moves: int, max_children: int):
+    def __init__(self, logic: BatchedGameLogic, n_games: int, max_moves: int, max_children: int, search_stats: bool = False):
         self.logic = logic
         self.n_games, self.max_moves, self.max_children = n_games, max_moves, max_children
+        self.search_stats = bool(search_stats)
         self._h = C.c_void_p()
-        check(lib().tafl_examples_create(logic._h, n_games, max_moves, max_children, C.byref(self._h)))
+        check(lib().tafl_examples_create_ex(logic._h, n_games, max_moves, max_children, abi.EXAMPLES_SEARCH_STATS if search_stats else 0, C.byref(self._h)))
         logic._batches.add(self)          # closed with the context, like its batches
 
     def close(self):
@@ -656,6 +662,39 @@ class Examples:
         check(lib().tafl_examples_read(self._h, idx.ctypes.data_as(vp), k, nc.ctypes.data_as(vp), ov.ctypes.data_as(vp), pl.ctypes.data_as(vp),
                                        mv.ctypes.data_as(vp), acts.ctypes.data_as(vp), vis.ctypes.data_as(vp)))
         return nc, ov, pl, mv, acts, vis
+
+    def read_stats(self, index):
+        """(q [k, max_children], prior [k, max_children]) float32 of the stored children of the examples `index`, in the order of
+        read()'s actions: Qsa and the root prior as the search held them (tafl_examples_read_stats; needs search_stats)."""
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        k, K = int(idx.size), self.max_children
+        q, pr = np.zeros((k, K), np.float32), np.zeros((k, K), np.float32)
+        vp = C.c_void_p
+        check(lib().tafl_examples_read_stats(self._h, idx.ctypes.data_as(vp), k, q.ctypes.data_as(vp), pr.ctypes.data_as(vp)))
+        return q, pr
+
+    def gather_stats(self, index, device: bool = False):
+        """(value [k], surprise [k]) float32 of the examples `index`: the visit-weighted mean of the stored children's Qsa and
+        KL(search policy || prior) in nats (tafl_examples_gather_stats; needs search_stats).  device as in gather()."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            idx = index.contiguous()
+            if idx.dtype != torch.int32 or not idx.is_cuda or idx.device.index != self.logic.device:
+                raise ValueError("gather_stats(device=True): index must be an int32 tensor on the context's device")
+            k = int(idx.numel())
+            value, surprise = torch.empty((k,), dtype=torch.float32, device=idx.device), torch.empty((k,), dtype=torch.float32, device=idx.device)
+            torch.cuda.current_stream(idx.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_examples_gather_stats(self._h, vp(idx.data_ptr()), k, vp(value.data_ptr()), vp(surprise.data_ptr()), 1))
+            self.logic.sync()
+            return value, surprise
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        k = int(idx.size)
+        value, surprise = np.zeros(k, np.float32), np.zeros(k, np.float32)
+        check(lib().tafl_examples_gather_stats(self._h, idx.ctypes.data_as(vp), k, value.ctypes.data_as(vp), surprise.ctypes.data_as(vp), 0))
+        return value, surprise
 
     def gather(self, index, sym=None, device: bool = False):
         """Minibatch rows (boards uint8 [k, n, n], sides uint8 [k], pi float32 [k, action_size], z float32 [k], final uint8 [k]) of the
@@ -885,6 +924,39 @@ class Pool:
         check(lib().tafl_pool_sample_weighted(self._h, seed, step, row_base, count, flags, *[a.ctypes.data_as(vp) for a in out], slot.ctypes.data_as(vp), sym.ctypes.data_as(vp),
                                               weight.ctypes.data_as(vp), C.cast(C.byref(total), vp), 0))
         return (*out, slot, sym, weight, int(total.value))
+
+    # ---- search statistics per row (tafl_pool_set_search_stats / _gather_stats / _weights_from_surprise) ----
+    def set_search_stats(self, on: bool = True):
+        """The pool carries the search value and the policy surprise of every row it ingests (only from Examples created with
+        search_stats).  Allowed while the pool holds no live row; clear() keeps the setting."""
+        check(lib().tafl_pool_set_search_stats(self._h, int(bool(on))))
+
+    def gather_stats(self, slots, device: bool = False):
+        """(value [k], surprise [k]) float32 of the rows in `slots`.  device=False: a slot that is not live raises.  device=True: int32
+        tensor in, tensors out; a slot that is not live gives zeros and counts in stats().bad_slot."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            sl = self._device_u32(slots, "gather_stats(device=True): slots")
+            k = int(sl.numel())
+            value, surprise = torch.empty((k,), dtype=torch.float32, device=sl.device), torch.empty((k,), dtype=torch.float32, device=sl.device)
+            torch.cuda.current_stream(sl.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_gather_stats(self._h, vp(sl.data_ptr()), k, vp(value.data_ptr()), vp(surprise.data_ptr()), 1))
+            self.logic.sync()
+            return value, surprise
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        k = int(sl.size)
+        value, surprise = np.zeros(k, np.float32), np.zeros(k, np.float32)
+        check(lib().tafl_pool_gather_stats(self._h, sl.ctypes.data_as(vp), k, value.ctypes.data_as(vp), surprise.ctypes.data_as(vp), 0))
+        return value, surprise
+
+    def weights_from_surprise(self, base: int, per_nat: float, generation: int = 0):
+        """Every live row of ingest `generation` (0: every live row) gets the weight min(2^32 - 1, base + floor(surprise * per_nat)): an
+        assignment on the device, nothing is read back.  Needs weighting and search statistics on."""
+        cfg = abi.TaflPoolSurpriseWeights(base=base, generation=generation, per_nat=per_nat)
+        check(lib().tafl_pool_weights_from_surprise(self._h, C.byref(cfg)))
+        self.logic.sync()
 
     def weight_stats(self) -> TaflPoolWeightCounters:
         """enabled, ingest_weight, total_weight, positive, bad_slot, rebuilds, device_bytes (all zero while weighting is off)."""

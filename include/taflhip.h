@@ -450,7 +450,37 @@ int tafl_mcts_policy_device_ex(tafl_batch* b, double temp, uint64_t tie_seed, ui
  *   ptrs_are_device = 0: all pointers are host pointers; an index that names no recorded example (or a sym above 7) fails the call with
  *   TAFL_ERR_INVALID_ARG before anything is written.  ptrs_are_device = 1: all pointers (index and sym included) are device pointers of
  *   the context's device, the kernel is enqueued on the context's stream (tafl_sync joins it) and nothing crosses PCIe; such an index
- *   gives an all-zero row and is counted in tafl_examples_stats.bad_index; sym is taken modulo 8. */
+ *   gives an all-zero row and is counted in tafl_examples_stats.bad_index; sym is taken modulo 8.
+ *
+ * Search value and policy surprise (examples that carry search statistics).
+ * tafl_examples_create_ex(ctx, n_games, max_moves, max_children, flags, out): flags = 0 is exactly tafl_examples_create.
+ *   TAFL_EXAMPLES_SEARCH_STATS adds two float32 arrays cq and cp laid out like the policy words ([(j * K + k) * G + g], K = max_children,
+ *   G = n_games): 8 * max_children bytes more per example, and 4 * n_games bytes of the recorder's bookkeeping, all counted in
+ *   tafl_examples_stats.device_bytes.  Unknown flag bits: TAFL_ERR_UNSUPPORTED.  Without the flag nothing of this section is allocated,
+ *   read, written or launched.
+ * What is recorded: every guided self-play run (tafl_gselfplay_begin, _begin_episodes, tafl_gmatch_begin; with root noise, a playout cap -
+ *   only full moves record -, forced playouts, the solver, an evaluation symmetry) that appends an example into such an object leaves,
+ *   for every stored child k (the visited root edges in ascending action order, after solver and forced pruning: the counts are n'),
+ *     cq[k] = (float)Qsa   and   cp[k] = (float)Ps[root][a]
+ *   as the root's edge held them when the move was made.  The self-play rounds are what they were: one more kernel per round, one lane
+ *   per game, reads the finished root's edge block, which stands until the next root is expanded.  Known and accepted: with root noise
+ *   Ps is the MIXED prior (what tafl_gmcts_root_priors reports), and under an evaluation symmetry it is indexed by the original action.
+ *   An example that overflowed or was dropped stores nothing.  tafl_examples_clear while a run records into the object is not supported.
+ *   tafl_selfplay_record (rollout mode has no priors) refuses such an object: TAFL_ERR_UNSUPPORTED.
+ * Two scalars per example, both 0 when the example has no stored policy (overflow, or no stored child):
+ *   value:     N = sum of the Nsa;  acc = 0;  for k ascending: acc = acc + (double)Nsa_k * (double)cq_k;  value = (float)(acc / (double)N).
+ *              No fused multiply-add: value is defined bit for bit.
+ *   surprise:  pi_k = (double)Nsa_k / (double)N;  s = sum over k ascending, in double, of pi_k * (log(pi_k) - log(max((double)cp_k, 2^-126)));
+ *              surprise = (float)max(s, 0.0).  This is KL(pi || P) over the stored children, in nats; it cannot be negative (log-sum
+ *              inequality, the stored priors sum to at most 1) but for rounding.  `log` is the float64 logarithm of the device's math library.
+ * tafl_examples_read_stats: q, prior [i * max_children + k] of the examples index[0 .. count) (0 beyond the stored children; either may
+ *   be NULL).  Host pointers, the slow path of tafl_examples_read.  An index that names no recorded example, or an object without the
+ *   flag: TAFL_ERR_INVALID_ARG.
+ * tafl_examples_gather_stats: value[i], surprise[i] of example index[i], one kernel, one lane per row (either output may be NULL).  Host
+ *   and device pointers as in tafl_examples_gather: a bad index fails the call with host pointers; with device pointers it writes zeros
+ *   and is counted in tafl_examples_stats.bad_index.  An object without the flag: TAFL_ERR_INVALID_ARG.
+ *   The training pool carries the two scalars and turns surprise into weights: tafl_pool_set_search_stats below. */
+#define TAFL_EXAMPLES_SEARCH_STATS 0x1u          /* tafl_examples_create_ex: keep Qsa and Ps of every stored child */
 typedef struct tafl_examples tafl_examples;      /* opaque, owned by the ctx's device */
 typedef struct tafl_selfplay_opts {
     uint64_t sample_seed;
@@ -480,6 +510,9 @@ int tafl_examples_read(tafl_examples* ex, const uint32_t* index, uint32_t count,
                        uint32_t* move_no, uint32_t* actions, uint32_t* visits);
 int tafl_examples_gather(tafl_examples* ex, const uint32_t* index, const uint8_t* sym, uint32_t count,
                          uint8_t* boards, uint8_t* sides, float* pi, float* z, uint8_t* final_, int ptrs_are_device);
+int tafl_examples_create_ex(tafl_ctx* ctx, uint32_t n_games, uint32_t max_moves, uint32_t max_children, uint32_t flags, tafl_examples** out);
+int tafl_examples_read_stats(tafl_examples* ex, const uint32_t* index, uint32_t count, float* q, float* prior);
+int tafl_examples_gather_stats(tafl_examples* ex, const uint32_t* index, uint32_t count, float* value, float* surprise, int ptrs_are_device);
 
 /* ---- guided MCTS: src/mcts.py:55-136 with the CALLER's network as nnet.predict (mcts.py:85), SURVEY.md section 8f rank 3 ---
  * Lock-step over the batch: each tafl_gmcts_step (i) expands every waiting leaf with the priors / value the caller computed
@@ -996,8 +1029,27 @@ int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device)
  *   an ingest, a trim, a clear, tafl_pool_set_weights or tafl_pool_set_weighting; that rebuild reads 16 bytes back.
  * tafl_pool_weight_stats: enabled, ingest_weight, total_weight = total, positive = live rows with a weight above 0, bad_slot, rebuilds,
  *   device_bytes = what weighting added.  All zero while weighting is off; switching it off and tafl_pool_clear zero bad_slot and rebuilds.
- * Not offered: saving and loading a pool, sampling without replacement, float weights, priorities computed by the library,
- *   de-duplication of positions, ingesting examples that are not final, a pool that spans devices. */
+ * Search statistics (off by default; while they are off the pool behaves and allocates as described above).
+ * tafl_pool_set_search_stats(pool, on): allowed only while live == 0 (otherwise TAFL_ERR_INVALID_ARG).  On allocates two float32 arrays
+ *   of `capacity` entries BESIDE the rows - value[s] and surprise[s] of the row in slot s; the row layout and the byte count of
+ *   tafl_pool_create do not change, tafl_pool_stats.device_bytes counts the 8 * capacity bytes - off frees them.  tafl_pool_clear keeps
+ *   the setting.  While it is on, tafl_pool_ingest refuses an examples object created without TAFL_EXAMPLES_SEARCH_STATS
+ *   (TAFL_ERR_INVALID_ARG, nothing is taken) and runs one more pass that writes, for every row the ingest stores, the value and the
+ *   surprise of its example - the two functions of tafl_examples_gather_stats, so a row's scalars equal what that call gives for its
+ *   source example on the same device.  While it is off an ingest ignores the arrays of such an object.
+ * tafl_pool_gather_stats: value[i], surprise[i] of the row in slot[i] (either may be NULL), with the rules of tafl_pool_get_weights for
+ *   slots that are not live: refused with host pointers (TAFL_ERR_INVALID_ARG), zeros and counted in tafl_pool_stats.bad_slot with device
+ *   pointers.  Search statistics off: TAFL_ERR_INVALID_ARG.
+ * tafl_pool_weights_from_surprise(pool, cfg): needs weighting AND search statistics on (otherwise TAFL_ERR_INVALID_ARG); per_nat
+ *   negative or NaN: TAFL_ERR_INVALID_ARG; flags or reserved words not 0: TAFL_ERR_UNSUPPORTED.  For every live slot s whose row has the
+ *   generation cfg->generation (0: every live slot)
+ *     x = (double)surprise[s] * per_nat;   wt[s] = min(2^32 - 1, base + (x < 2^32 ? (uint64)x : 2^32 - 1))
+ *   which is an ASSIGNMENT, not the maximum rule of tafl_pool_set_weights; the other slots are unchanged.  One kernel over the slots on
+ *   the context's stream, nothing is read back; the sums behind the weighted search are rebuilt by the next weighted sample, as after
+ *   tafl_pool_set_weights.
+ * Not offered: saving and loading a pool, sampling without replacement, float weights,
+ *   de-duplication of positions, ingesting examples that are not final, a pool that spans devices, surprise over unvisited children,
+ *   decay of weights by generation. */
 typedef struct tafl_pool tafl_pool;                 /* opaque, owned by the ctx's device */
 typedef struct tafl_pool_stats {
     uint64_t written;          /* rows ever taken by ingests (also those that fell out of the window) */
@@ -1045,6 +1097,16 @@ int tafl_pool_sample_weighted(tafl_pool* pool, uint64_t seed, uint64_t step, uin
                               uint8_t* boards, uint8_t* sides, float* pi, float* z, uint32_t* out_slot, uint8_t* out_sym,
                               uint32_t* out_weight, uint64_t* out_total, int ptrs_are_device);
 int tafl_pool_weight_stats(tafl_pool* pool, tafl_pool_weight_counters* out);
+typedef struct tafl_pool_surprise_weights {
+    uint32_t base;             /* the weight of a row without surprise */
+    uint32_t generation;       /* only the rows of this ingest; 0: every live row */
+    double per_nat;            /* weight added per nat of surprise, >= 0 */
+    uint32_t flags;            /* 0 */
+    uint32_t _reserved[3];     /* 0 */
+} tafl_pool_surprise_weights;                       /* 32 bytes */
+int tafl_pool_set_search_stats(tafl_pool* pool, int on);                              /* 0: off (the default) */
+int tafl_pool_gather_stats(tafl_pool* pool, const uint32_t* slot, uint32_t count, float* value, float* surprise, int ptrs_are_device);
+int tafl_pool_weights_from_surprise(tafl_pool* pool, const tafl_pool_surprise_weights* cfg);
 
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
