@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflPoolSurpriseWeights, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolDedupCfg, TaflPoolDedupResult, TaflPoolDedupWeights, TaflPoolIngestResult, TaflPoolStats, TaflPoolSurpriseWeights, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +118,9 @@ SYMBOLS = [
     ("tafl_pool_set_search_stats", _i32, [_vp, _i32]),
     ("tafl_pool_gather_stats", _i32, [_vp, _vp, _u32, _vp, _vp, _i32]),
     ("tafl_pool_weights_from_surprise", _i32, [_vp, _P(TaflPoolSurpriseWeights)]),
+    ("tafl_pool_dedup", _i32, [_vp, _P(TaflPoolDedupCfg), _P(TaflPoolDedupResult)]),
+    ("tafl_pool_gather_dedup", _i32, [_vp, _vp, _u32, _vp, _vp, _vp, _i32]),
+    ("tafl_pool_weights_from_dedup", _i32, [_vp, _P(TaflPoolDedupWeights)]),
     ("tafl_root_noise_eval", _i32, [_vp, _P(TaflRootNoise), _vp, _i32]),
     ("tafl_gmcts_root_priors", _i32, [_vp, _vp, _i32]),
     ("tafl_replay_append", _i32, [C.c_char_p, _P(_u8), _u8, _P(_u8), _u32, _u8, _u8, _u64]),

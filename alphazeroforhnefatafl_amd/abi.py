@@ -258,8 +258,27 @@ class TaflPoolSurpriseWeights(C.Structure):
     _fields_ = [("base", C.c_uint32), ("generation", C.c_uint32), ("per_nat", C.c_double), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 3)]
 
 
+class TaflPoolDedupCfg(C.Structure):
+    """tafl_pool_dedup_cfg: how tafl_pool_dedup makes its keys."""
+    _fields_ = [("flags", C.c_uint32), ("key_bits", C.c_uint32), ("_reserved", C.c_uint32 * 6)]
+
+
+class TaflPoolDedupResult(C.Structure):
+    """tafl_pool_dedup_result: what one tafl_pool_dedup found."""
+    _fields_ = [("live", C.c_uint64), ("distinct", C.c_uint64), ("largest", C.c_uint64), ("collisions", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("_reserved", C.c_uint64 * 3)]
+
+
+class TaflPoolDedupWeights(C.Structure):
+    """tafl_pool_dedup_weights: the rule of tafl_pool_weights_from_dedup."""
+    _fields_ = [("scale", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 6)]
+
+
 EXAMPLES_SEARCH_STATS = 0x1      # tafl_examples_create_ex flags: keep Qsa and Ps of every stored child
 POOL_SAMPLE_SYM = 0x1            # tafl_pool_sample flags: draw one of the eight symmetries per row
+POOL_DEDUP_SYMMETRIES = 0x1      # tafl_pool_dedup flags: images of a position under the board symmetries are one group
+POOL_DEDUP_DIVIDE = 0x1          # tafl_pool_weights_from_dedup flags: divide the weight a row has by its group's size
+POOL_DEDUP_REPRESENTATIVES = 0x2 # tafl_pool_weights_from_dedup flags: `scale` for the newest row of a group, 0 for the others
 
 EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_effects": 40,
                   "tafl_rollout_result": 8, "tafl_root_child": 24, "tafl_mcts_params": 32,
@@ -269,7 +288,7 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
                   "tafl_eval_symmetry": 32,
                   "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32, "tafl_pool_weights": 32, "tafl_pool_weight_counters": 64,
-                  "tafl_pool_surprise_weights": 32}
+                  "tafl_pool_surprise_weights": 32, "tafl_pool_dedup_cfg": 32, "tafl_pool_dedup_result": 64, "tafl_pool_dedup_weights": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -282,7 +301,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_solver", TaflSolver), ("tafl_solver_stats", TaflSolverStats), ("tafl_eval_symmetry", TaflEvalSymmetry),
                     ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult),
                     ("tafl_pool_weights", TaflPoolWeights), ("tafl_pool_weight_counters", TaflPoolWeightCounters),
-                    ("tafl_pool_surprise_weights", TaflPoolSurpriseWeights)]:
+                    ("tafl_pool_surprise_weights", TaflPoolSurpriseWeights), ("tafl_pool_dedup_cfg", TaflPoolDedupCfg),
+                    ("tafl_pool_dedup_result", TaflPoolDedupResult), ("tafl_pool_dedup_weights", TaflPoolDedupWeights)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

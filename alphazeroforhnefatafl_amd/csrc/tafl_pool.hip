@@ -289,6 +289,139 @@ __global__ __launch_bounds__(256) void k_poolw_draw(PoolWeights W, uint32_t firs
     }
 }
 
+// ---- de-duplication: the key of every live row, the groups in a hash table, the per-slot outputs (tafl_pool.hpp: pooldd_*) -----------------
+#ifndef TAFL_POOLDD_AGGREGATE
+#define TAFL_POOLDD_AGGREGATE 1      /* how k_pooldd_insert joins equal keys inside a wave: 1 runs of neighbouring lanes; the measurement compares with
+                                        0 (every lane inserts its own row) and 2 (a loop over the wave's distinct keys, one leader each) */
+#endif
+// the slot of the live row of age rank a (first = the slot of rank 0)
+__device__ __forceinline__ uint32_t pooldd_slot(uint32_t first, unsigned long long a, uint32_t C) { const unsigned long long s = first + a; return (uint32_t)(s >= C ? s - C : s); }
+// Pass 1: key[s] and canon[s] of every live row.  A workgroup stages the board words and the info word of POOLDD_ROWS rows of consecutive
+// age ranks - consecutive slots, contiguous memory but for the ring's end - in LDS with 16-byte loads, Q quads per row; eight lanes per
+// row fold one symmetry each with byte reads from LDS and take the minimum (hash, symmetry) across the eight.  Without symmetries only
+// the first lane of the eight folds.
+__global__ __launch_bounds__(256) void k_pooldd_key(PoolMem P, uint32_t first, uint32_t live, uint32_t n, uint32_t Q, uint32_t symmetries, uint32_t key_bits,
+                                                    unsigned long long* key, uint8_t* canon) {
+    extern __shared__ __align__(16) uint32_t dd_rows[];                       // [POOLDD_ROWS][4 * Q]
+    const uint32_t sub = threadIdx.x & 7u, lr = threadIdx.x >> 3, qpr = P.RW / 4u;
+    const uint4* rows = reinterpret_cast<const uint4*>(P.rows);
+    for (unsigned long long a0 = (unsigned long long)blockIdx.x * POOLDD_ROWS; a0 < live; a0 += (unsigned long long)gridDim.x * POOLDD_ROWS) {      // (block-uniform)
+        const uint32_t nr = live - a0 < POOLDD_ROWS ? (uint32_t)(live - a0) : (uint32_t)POOLDD_ROWS;
+        for (uint32_t q = threadIdx.x; q < nr * Q; q += 256) {
+            const uint32_t row = q / Q, wq = q % Q;
+            reinterpret_cast<uint4*>(dd_rows)[q] = rows[(size_t)pooldd_slot(first, a0 + row, P.C) * qpr + wq];
+        }
+        __syncthreads();
+        if (lr < nr) {                                                          // (the eight lanes of a row together)
+            const uint32_t* row = dd_rows + lr * 4u * Q;
+            unsigned long long h = ~0ull; uint32_t c = sub;
+            if (sub == 0u || symmetries) h = pooldd_hash(reinterpret_cast<const uint8_t*>(row), sub, n, P.BW, pool_row_side(row, P.BW));
+            if (symmetries)
+                for (uint32_t d = 1; d < 8u; d <<= 1) {
+                    const unsigned long long oh = __shfl_xor(h, d, 8); const uint32_t oc = __shfl_xor(c, d, 8);
+                    if (oh < h || (oh == h && oc < c)) { h = oh; c = oc; }
+                }
+            if (sub == 0u) { const uint32_t s = pooldd_slot(first, a0 + lr, P.C); key[s] = pooldd_key(h, key_bits); canon[s] = (uint8_t)c; }
+        }
+        __syncthreads();
+    }
+}
+// Pass 2: one lane per live row, in the order of the age ranks, joins its key's entry (pooldd_insert) and stores the entry's index.  An
+// ingest stores the examples e = j * G + g in ascending order, so the copies of a position reached by neighbouring games at the same move
+// - the start position above all - sit in neighbouring slots: a run of equal keys in neighbouring lanes is inserted once, by its first
+// lane, with the run's counts (ballots and popcounts, no loop), and rows without such a neighbour go on in parallel as they would alone.
+template <int AGG>
+__global__ __launch_bounds__(256) void k_pooldd_insert(PoolMem P, PoolDedupTable T, uint32_t first, uint32_t live, const unsigned long long* key, uint32_t* ent) {
+    const uint32_t lane = threadIdx.x & 63u;
+    for (unsigned long long a0 = (unsigned long long)blockIdx.x * 256 + (threadIdx.x - lane); a0 < live; a0 += (unsigned long long)gridDim.x * 256) {     // (wave-uniform)
+        const unsigned long long a = a0 + lane;
+        const bool in = a < live;
+        uint32_t s = 0; unsigned long long k = 0; float z = 0.0f;
+        if (in) { s = pooldd_slot(first, a, P.C); k = key[s]; z = pool_row_z(P.rows + (size_t)s * P.RW, P.BW); }
+        const bool won = z == 1.0f, lost = z == -1.0f;
+        uint32_t pos = 0;
+        if constexpr (AGG == 2) {
+            unsigned long long todo = __ballot(in);
+            while (todo) {                                                      // (wave-uniform: one turn per distinct key of the wave)
+                const int leader = __ffsll((long long)todo) - 1;
+                const unsigned long long lk = __shfl(k, leader, 64);
+                const bool same = in && k == lk;
+                const unsigned long long m = __ballot(same), mw = __ballot(same && won), ml = __ballot(same && lost);
+                uint32_t e = 0;
+                if (lane == (uint32_t)leader)
+                    e = pooldd_insert(T, lk, (uint32_t)__popcll(m), (uint32_t)__popcll(mw), (uint32_t)__popcll(ml), (uint32_t)a0 + 63u - (uint32_t)__clzll((long long)m));
+                e = __shfl(e, leader, 64);
+                if (same) pos = e;
+                todo &= ~m;
+            }
+        } else if constexpr (AGG == 1) {
+            const unsigned long long prev = __shfl_up(k, 1, 64);
+            const bool head = in && (lane == 0u || k != prev);                  // (the lanes that are in are the first ones of the wave)
+            const unsigned long long heads = __ballot(head), inm = __ballot(in), mw = __ballot(in && won), ml = __ballot(in && lost);
+            uint32_t e = 0;
+            if (head) {
+                const unsigned long long above = lane == 63u ? 0ull : heads & (~0ull << (lane + 1u));
+                const uint32_t end = above ? (uint32_t)__ffsll((long long)above) - 1u : 64u;
+                const unsigned long long run = (end == 64u ? ~0ull : (1ull << end) - 1ull) & (~0ull << lane) & inm;
+                e = pooldd_insert(T, k, (uint32_t)__popcll(run), (uint32_t)__popcll(run & mw), (uint32_t)__popcll(run & ml), (uint32_t)a0 + 63u - (uint32_t)__clzll((long long)run));
+            }
+            const unsigned long long upto = heads & ((2ull << lane) - 1ull);    // (lane 63: 2 << 63 wraps to 0, the mask is all ones)
+            const uint32_t hl = upto ? 63u - (uint32_t)__clzll((long long)upto) : 0u;
+            pos = __shfl(e, hl, 64);
+        } else if (in) pos = pooldd_insert(T, k, 1u, won ? 1u : 0u, lost ? 1u : 0u, (uint32_t)a);
+        if (in) ent[s] = pos;
+    }
+}
+// Pass 3: one lane per live row reads its entry: rep, mult and zmean of its slot; a row that is not its group's representative compares
+// its side and canonical image with the representative's.  A wave counts distinct and collisions by
+// ballot and keeps its largest mult over all its turns, and flushes once at its end.
+__global__ __launch_bounds__(256) void k_pooldd_finish(PoolMem P, PoolDedupTable T, uint32_t first, uint32_t live, uint32_t n, const uint32_t* ent, const uint8_t* canon,
+                                                       uint32_t* rep, uint32_t* mult, float* zmean, unsigned long long* res) {
+    const uint32_t lane = threadIdx.x & 63u;
+    uint32_t nd = 0, nc = 0, largest = 0;                                       // of this wave, over all its turns
+    for (unsigned long long a0 = (unsigned long long)blockIdx.x * 256 + (threadIdx.x - lane); a0 < live; a0 += (unsigned long long)gridDim.x * 256) {     // (wave-uniform)
+        const unsigned long long a = a0 + lane;
+        bool is_rep = false, differs = false;
+        uint32_t m = 0;
+        if (a < live) {
+            const uint32_t s = pooldd_slot(first, a, P.C), e = ent[s], r = pooldd_slot(first, T.newest[e], P.C);
+            m = T.count[e];
+            rep[s] = r; mult[s] = m; zmean[s] = pooldd_zmean(m, T.wins[e], T.losses[e]);
+            is_rep = r == s;
+            if (!is_rep) differs = !pooldd_same(P.rows + (size_t)s * P.RW, canon[s], P.rows + (size_t)r * P.RW, canon[r], n, P.BW);
+        }
+        nd += (uint32_t)__popcll(__ballot(is_rep)); nc += (uint32_t)__popcll(__ballot(differs));
+        largest = m > largest ? m : largest;
+    }
+    for (uint32_t d = 32; d; d >>= 1) { const uint32_t o = __shfl_xor(largest, d, 64); largest = o > largest ? o : largest; }
+    if (lane == 0u) {                                                           // (at most 8 192 waves: the grid is capped)
+        if (nd) atomicAdd(&res[PDD_DISTINCT], (unsigned long long)nd);
+        if (nc) atomicAdd(&res[PDD_COLLISIONS], (unsigned long long)nc);
+        if (largest) atomicMax(&res[PDD_LARGEST], (unsigned long long)largest);
+    }
+}
+// tafl_pool_weights_from_dedup: every live slot is ASSIGNED pooldd_weight
+__global__ __launch_bounds__(256) void k_pooldd_weights(uint32_t* wt, const uint32_t* rep, const uint32_t* mult, uint32_t first, unsigned long long live, uint32_t C, uint32_t scale,
+                                                        uint32_t flags) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < C; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = (uint32_t)i;
+        if (!pool_slot_live_from(s, first, live, C)) continue;
+        wt[s] = pooldd_weight(wt[s], mult[s], rep[s] == s, scale, flags);
+    }
+}
+// tafl_pool_gather_dedup: zeros for a slot that is not live, counted
+__global__ __launch_bounds__(256) void k_pooldd_gather(const uint32_t* drep, const uint32_t* dmult, const float* dz, unsigned long long* counters, const uint32_t* slot, uint32_t count,
+                                                       uint32_t first, unsigned long long live, uint32_t C, uint32_t* rep, uint32_t* mult, float* zmean) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        const bool ok = pool_slot_live_from(s, first, live, C);
+        if (!ok) atomicAdd(&counters[POOL_BAD_SLOT], 1ull);
+        if (rep) rep[i] = ok ? drep[s] : 0u;
+        if (mult) mult[i] = ok ? dmult[s] : 0u;
+        if (zmean) zmean[i] = ok ? dz[s] : 0.0f;
+    }
+}
+
 struct tafl_pool {
     tafl_ctx* ctx;
     PoolMem mem;
@@ -313,6 +446,15 @@ struct tafl_pool {
     // search statistics per row (tafl_pool_set_search_stats; off: no buffer of it exists): value and surprise of the row in slot s
     bool search_stats = false;
     DevBuf s_value, s_surprise, g_s;     // g_s: staging of the second scalar of a host-pointer tafl_pool_gather_stats
+    // de-duplication (tafl_pool_dedup; before the first call and after tafl_pool_dedup(pool, NULL, ..): no buffer of it exists)
+    bool dd_valid = false;               // a result stands: no ingest, trim or clear since the last tafl_pool_dedup
+    DevBuf dd_rep, dd_mult, dd_zmean, dd_canon, dd_key, dd_ent, dd_table, dd_res, dd_stage;     // dd_stage: slot, rep, mult, zmean of a host-pointer gather
+    size_t dedup_bytes = 0;
+    int ddneed(DevBuf& d, size_t bytes) { const size_t before = d.cap; const int rc = need(d, bytes); dedup_bytes += d.cap - before; return rc; }
+    void ddfree() {
+        for (DevBuf* d : {&dd_rep, &dd_mult, &dd_zmean, &dd_canon, &dd_key, &dd_ent, &dd_table, &dd_res, &dd_stage}) { device_bytes -= d->cap; d->release(); }
+        dedup_bytes = 0; dd_valid = false;
+    }
     uint32_t first_live() const { return book.live ? pool_first_live(book.written, book.live, mem.C) : 0u; }
 };
 
@@ -401,6 +543,7 @@ int tafl_pool_clear(tafl_pool* p) {
     HIPCHK(hipMemsetAsync(p->counters.p, 0, 8 * POOL_COUNTERS, p->ctx->stream));
     if (p->weighting) HIPCHK(hipMemsetAsync(p->wres.p, 0, 8 * PW_WORDS, p->ctx->stream));
     p->book.clear(); p->skipped_open = p->skipped_overflow = 0;
+    p->dd_valid = false;
     p->dirty = true; p->total = p->positive = p->rebuilds = 0;          // (the setting of the weighting and the stored weights stay)
     return sync_ok(p->ctx);
 }
@@ -426,6 +569,7 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     if (p->search_stats && !(ex->flags & TAFL_EXAMPLES_SEARCH_STATS))
         return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the pool carries search statistics, the examples object was created without TAFL_EXAMPLES_SEARCH_STATS");
     tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
+    p->dd_valid = false;
     const uint32_t E = ex->n_games * ex->max_moves, nb = (uint32_t)(((unsigned long long)E + POOL_TILE - 1) / POOL_TILE);       // (E fits 32 bits: tafl_examples_create)
     POOLNEED(p->blk, 16 * (size_t)nb);
     uint32_t* taken = p->blk.as<uint32_t>(); uint32_t* open = taken + nb; uint32_t* over = open + nb; uint32_t* prefix = over + nb;
@@ -456,7 +600,7 @@ int tafl_pool_trim(tafl_pool* p, uint32_t keep_generations) {
     POOLCHK(p, "tafl_pool_trim");
     if (keep_generations == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_trim: keep_generations must be at least 1");
     p->book.trim(keep_generations);
-    p->dirty = true;
+    p->dirty = true; p->dd_valid = false;
     return TAFL_OK;
 }
 
@@ -720,6 +864,89 @@ int tafl_pool_weights_from_surprise(tafl_pool* p, const tafl_pool_surprise_weigh
     if (p->book.live == 0) return TAFL_OK;
     hipLaunchKernelGGL(k_poolw_from_surprise, dim3(poolw_grid(p->mem.C)), dim3(256), 0, p->ctx->stream, p->wmem.wt, p->s_surprise.as<const float>(), (const uint32_t*)p->mem.rows, p->mem.RW,
                        p->mem.BW + (uint32_t)PR_GENERATION, p->first_live(), (unsigned long long)p->book.live, p->mem.C, cfg->base, cfg->generation, cfg->per_nat);
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
+
+int tafl_pool_dedup(tafl_pool* p, const tafl_pool_dedup_cfg* cfg, tafl_pool_dedup_result* out) {
+    POOLCHK(p, "tafl_pool_dedup");
+    tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
+    if (!cfg) {
+        HIPCHK(hipStreamSynchronize(s));
+        p->ddfree();
+        if (out) memset(out, 0, sizeof *out);
+        return TAFL_OK;
+    }
+    if (cfg->flags & ~(uint32_t)TAFL_POOL_DEDUP_SYMMETRIES) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_dedup: unknown flag bits");
+    if (cfg->key_bits > 64u) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_dedup: key_bits must be in 0..64");
+    for (uint32_t r : cfg->_reserved) if (r) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_dedup: reserved words must be 0");
+    if (p->book.live == 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_dedup: the pool holds no live row");
+    if ((uint64_t)p->mem.C > (1ull << 30)) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_dedup: pools of more than 2^30 rows are not supported");
+    p->dd_valid = false;
+    const size_t C = p->mem.C;
+    const uint32_t live = (uint32_t)p->book.live, first = p->first_live(), TS = pooldd_table_size(live);
+    if (p->ddneed(p->dd_rep, 4 * C) || p->ddneed(p->dd_mult, 4 * C) || p->ddneed(p->dd_zmean, 4 * C) || p->ddneed(p->dd_canon, C) || p->ddneed(p->dd_key, 8 * C) ||
+        p->ddneed(p->dd_ent, 4 * C) || p->ddneed(p->dd_table, pooldd_table_bytes(pooldd_table_size(C))) || p->ddneed(p->dd_res, 8 * PDD_WORDS)) {
+        p->ddfree();
+        return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_pool_dedup)");
+    }
+    const PoolDedupTable T = pooldd_table(p->dd_table.p, TS);
+    unsigned long long* res = p->dd_res.as<unsigned long long>();
+    HIPCHK(hipMemsetAsync(p->dd_table.p, 0, pooldd_table_bytes(TS), s));
+    HIPCHK(hipMemsetAsync(res, 0, 8 * PDD_WORDS, s));
+    const uint32_t Q = (p->mem.BW + 1u + 3u) / 4u;                             // the board words and the info word, in quads
+    const uint32_t kgrid = std::min<uint32_t>((live + POOLDD_ROWS - 1u) / POOLDD_ROWS, 16384u), grid = poolw_grid(live);
+    hipLaunchKernelGGL(k_pooldd_key, dim3(kgrid), dim3(256), (size_t)POOLDD_ROWS * 16u * Q, s, p->mem, first, live, c->n, Q, cfg->flags & (uint32_t)TAFL_POOL_DEDUP_SYMMETRIES,
+                       cfg->key_bits, p->dd_key.as<unsigned long long>(), p->dd_canon.as<uint8_t>());
+    hipLaunchKernelGGL(k_pooldd_insert<TAFL_POOLDD_AGGREGATE>, dim3(grid), dim3(256), 0, s, p->mem, T, first, live, p->dd_key.as<const unsigned long long>(), p->dd_ent.as<uint32_t>());
+    hipLaunchKernelGGL(k_pooldd_finish, dim3(grid), dim3(256), 0, s, p->mem, T, first, live, c->n, p->dd_ent.as<const uint32_t>(), p->dd_canon.as<const uint8_t>(),
+                       p->dd_rep.as<uint32_t>(), p->dd_mult.as<uint32_t>(), p->dd_zmean.as<float>(), res);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[PDD_WORDS];
+    HIPCHK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    p->dd_valid = true;
+    if (out) {
+        memset(out, 0, sizeof *out);
+        out->live = live; out->distinct = h[PDD_DISTINCT]; out->largest = h[PDD_LARGEST]; out->collisions = h[PDD_COLLISIONS]; out->device_bytes = p->dedup_bytes;
+    }
+    return TAFL_OK;
+}
+
+int tafl_pool_gather_dedup(tafl_pool* p, const uint32_t* slot, uint32_t count, uint32_t* rep, uint32_t* mult, float* zmean, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_gather_dedup");
+    if (!p->dd_valid) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_dedup: no de-duplication result stands (tafl_pool_dedup after the last ingest, trim or clear)");
+    if (!slot && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_dedup: null slot");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = p->ctx->stream;
+    uint32_t* dr = rep; uint32_t* dm = mult; float* dz = zmean;
+    if (!ptrs_are_device) {
+        for (uint32_t i = 0; i < count; ++i)
+            if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_dedup: slot " + std::to_string(slot[i]) + " (row " + std::to_string(i) + ") is not live");
+        if (p->ddneed(p->dd_stage, 16 * (size_t)count)) return fail(TAFL_ERR_OOM, "hipMalloc(workspace) failed");
+        uint32_t* st = p->dd_stage.as<uint32_t>();
+        HIPCHK(hipMemcpyAsync(st, slot, 4 * (size_t)count, hipMemcpyHostToDevice, s));
+        slot = st; dr = st + count; dm = dr + count; dz = reinterpret_cast<float*>(dm + count);
+    }
+    hipLaunchKernelGGL(k_pooldd_gather, dim3(poolw_grid(count)), dim3(256), 0, s, p->dd_rep.as<const uint32_t>(), p->dd_mult.as<const uint32_t>(), p->dd_zmean.as<const float>(),
+                       p->mem.counters, slot, count, p->first_live(), (unsigned long long)p->book.live, p->mem.C, dr, dm, dz);
+    HIPCHK(hipGetLastError());
+    if (!ptrs_are_device) { COPY_OUT(rep, dr, count, s); COPY_OUT(mult, dm, count, s); COPY_OUT(zmean, dz, count, s); HIPCHK(hipStreamSynchronize(s)); }
+    return TAFL_OK;
+}
+
+int tafl_pool_weights_from_dedup(tafl_pool* p, const tafl_pool_dedup_weights* cfg) {
+    POOLCHK(p, "tafl_pool_weights_from_dedup");
+    if (!cfg) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_dedup: null argument");
+    if (cfg->flags & ~(uint32_t)(TAFL_POOL_DEDUP_DIVIDE | TAFL_POOL_DEDUP_REPRESENTATIVES)) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_weights_from_dedup: unknown flag bits");
+    if (cfg->flags == (uint32_t)(TAFL_POOL_DEDUP_DIVIDE | TAFL_POOL_DEDUP_REPRESENTATIVES))
+        return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_weights_from_dedup: TAFL_POOL_DEDUP_DIVIDE and TAFL_POOL_DEDUP_REPRESENTATIVES exclude each other");
+    for (uint32_t r : cfg->_reserved) if (r) return fail(TAFL_ERR_UNSUPPORTED, "tafl_pool_weights_from_dedup: reserved words must be 0");
+    if (!p->weighting) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_dedup: weighting is off (tafl_pool_set_weighting)");
+    if (!p->dd_valid) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_weights_from_dedup: no de-duplication result stands (tafl_pool_dedup after the last ingest, trim or clear)");
+    p->dirty = true;
+    hipLaunchKernelGGL(k_pooldd_weights, dim3(poolw_grid(p->mem.C)), dim3(256), 0, p->ctx->stream, p->wmem.wt, p->dd_rep.as<const uint32_t>(), p->dd_mult.as<const uint32_t>(), p->first_live(),
+                       (unsigned long long)p->book.live, p->mem.C, cfg->scale, cfg->flags);
     HIPCHK(hipGetLastError());
     return TAFL_OK;
 }

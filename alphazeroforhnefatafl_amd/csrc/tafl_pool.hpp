@@ -2,7 +2,8 @@
 // tafl_examples object and sampled uniformly under random board symmetries.  What is decided per example, per row and per drawn row is
 // here: which recorded example an ingest takes (pool_take), the words of a row (pool_row_word), the draw (pool_draw), which slots are
 // live (pool_slot_live) and what a row writes into a minibatch (pool_out_tile, pool_out_pi); for weighted sampling the masked weight
-// (pool_eff), the weighted draw (pool_wdraw) and the steps of its search (pool_wsearch_*, pool_wpick).  __host__ __device__ like
+// (pool_eff), the weighted draw (pool_wdraw) and the steps of its search (pool_wsearch_*, pool_wpick); for de-duplication the key of
+// a row, the table insert and the group's mean result (pooldd_*).  __host__ __device__ like
 // tafl_examples.hpp: the kernels of tafl_pool.hip run these functions one example / word / tile / policy entry / probe per lane,
 // tests/hostsim_pool and tests/hostsim_pool_weights run them in serial loops on the CPU.
 #pragma once
@@ -160,6 +161,133 @@ static TAFL_HD uint32_t pool_surprise_weight(float surprise, uint32_t base, doub
     const double x = (double)surprise * per_nat;
     const uint64_t add = x < 4294967296.0 ? (uint64_t)x : 0xFFFFFFFFull, w = (uint64_t)base + add;
     return w < 0xFFFFFFFFull ? (uint32_t)w : 0xFFFFFFFFu;
+}
+
+// ---- de-duplication (tafl_pool_dedup / _gather_dedup / _weights_from_dedup; the text in include/taflhip.h is normative) --
+// Live rows with equal keys form a group; a key is a 64-bit hash of the side to move and the board bytes (under the symmetry that gives the
+// smallest hash, with TAFL_POOL_DEDUP_SYMMETRIES).  The groups are found in an open-addressing table of integer counters, so that what a
+// row reads back depends on the pool's contents alone, never on the order the rows were inserted in.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define TAFL_POOLDD_CAS(p, cmp, v) atomicCAS((p), (unsigned long long)(cmp), (unsigned long long)(v))
+#define TAFL_POOLDD_ADD(p, v) atomicAdd((p), (v))
+#define TAFL_POOLDD_MAX(p, v) atomicMax((p), (v))
+#else
+#define TAFL_POOLDD_CAS(p, cmp, v) (*(p) == (unsigned long long)(cmp) ? (*(p) = (unsigned long long)(v), (unsigned long long)(cmp)) : *(p))
+#define TAFL_POOLDD_ADD(p, v) (*(p) += (v))
+#define TAFL_POOLDD_MAX(p, v) (*(p) = *(p) < (v) ? (v) : *(p))
+#endif
+enum { PDD_DISTINCT = 0, PDD_LARGEST = 1, PDD_COLLISIONS = 2, PDD_WORDS = 4 };
+enum { POOLDD_ROWS = 32 };           // rows a workgroup of k_pooldd_key stages: eight lanes per row
+// the table of one tafl_pool_dedup call: TS entries, all zero before the first insert (no key is 0)
+struct PoolDedupTable {
+    unsigned long long* key;         // [TS] 0: free
+    uint32_t* count;                 // [TS] members
+    uint32_t* wins;                  // [TS] members with z == 1.0f
+    uint32_t* losses;                // [TS] members with z == -1.0f
+    uint32_t* newest;                // [TS] the largest age rank of a member
+    uint32_t TS;
+};
+static TAFL_HD size_t pooldd_table_bytes(uint32_t TS) { return 24 * (size_t)TS; }
+static TAFL_HD PoolDedupTable pooldd_table(void* base, uint32_t TS) {
+    PoolDedupTable T;
+    T.key = static_cast<unsigned long long*>(base);
+    T.count = reinterpret_cast<uint32_t*>(T.key + TS); T.wins = T.count + TS; T.losses = T.wins + TS; T.newest = T.losses + TS; T.TS = TS;
+    return T;
+}
+// the table of a call over `live` rows: the power of two that is at least 2 * live (at least 64)
+static TAFL_HD uint32_t pooldd_table_size(uint64_t live) { uint64_t ts = 64; while (ts < 2 * live) ts <<= 1; return (uint32_t)ts; }
+// the splitmix64 finaliser
+static TAFL_HD uint64_t pooldd_mix64(uint64_t x) {
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull; x ^= x >> 27; x *= 0x94D049BB133111EBull; x ^= x >> 31;
+    return x;
+}
+// sym_tile is a bijection of the tiles; its inverse is sym_tile of this symmetry (the two rotations by a quarter turn swap, the others
+// are their own inverse)
+static TAFL_HD uint32_t pooldd_sym_inverse(uint32_t sym) { return (sym == 5u || sym == 6u) ? sym ^ 3u : sym; }
+// sym_tile(sym, r * n + c, n) for a tile at hand as (r, c): no division
+static TAFL_HD uint32_t pooldd_sym_rc(uint32_t sym, uint32_t r, uint32_t c, uint32_t n) {
+    if (sym & 4u) { const uint32_t x = r; r = c; c = x; }
+    if (sym & 1u) r = n - 1u - r;
+    if (sym & 2u) c = n - 1u - c;
+    return r * n + c;
+}
+// h(sym) of a row: the image under sym has byte b[t] at tile sym_tile(sym, t, n), so its tile u holds b[sym_tile(inverse, u, n)]; the
+// image is folded word by word, four tiles per word, zero bytes beyond n * n.  `b`: the row's board bytes, tile t at b[t].
+static TAFL_HD uint64_t pooldd_hash(const uint8_t* b, uint32_t sym, uint32_t n, uint32_t BW, uint32_t side) {
+    const uint32_t inv = pooldd_sym_inverse(sym);
+    uint64_t x = 0x9E3779B97F4A7C15ull ^ (uint64_t)side;
+    uint32_t r = 0, c = 0;
+    for (uint32_t i = 0; i < BW; ++i) {
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < 4u; ++k) {
+            if (r >= n) break;
+            w |= (uint32_t)b[inv ? pooldd_sym_rc(inv, r, c, n) : r * n + c] << (8u * k);
+            if (++c == n) { c = 0; ++r; }
+        }
+        x = pooldd_mix64(x ^ (uint64_t)w);
+    }
+    return x;
+}
+// the key of a hash: its low key_bits bits (1..64, 0 means 64), 1 in place of 0
+static TAFL_HD uint64_t pooldd_key(uint64_t h, uint32_t key_bits) {
+    if (key_bits != 0u && key_bits < 64u) h &= (1ull << key_bits) - 1ull;
+    return h ? h : 1ull;
+}
+// key and canon of a row, all by one caller (the kernel gives a symmetry to each of eight lanes and takes the minimum across them)
+static TAFL_HD uint64_t pooldd_row_key(const uint32_t* row, uint32_t n, uint32_t BW, bool symmetries, uint32_t key_bits, uint32_t& canon) {
+    const uint8_t* b = reinterpret_cast<const uint8_t*>(row);
+    const uint32_t side = pool_row_side(row, BW);
+    uint64_t best = pooldd_hash(b, 0u, n, BW, side);
+    canon = 0;
+    if (symmetries)
+        for (uint32_t s = 1; s < 8u; ++s) { const uint64_t h = pooldd_hash(b, s, n, BW, side); if (h < best) { best = h; canon = s; } }
+    return pooldd_key(best, key_bits);
+}
+// the rows a and b have the same side to move and the same canonical image (each under its own canon)
+static TAFL_HD bool pooldd_same(const uint32_t* a, uint32_t canon_a, const uint32_t* b, uint32_t canon_b, uint32_t n, uint32_t BW) {
+    if (pool_row_side(a, BW) != pool_row_side(b, BW)) return false;
+    if (canon_a == canon_b) {                                                   // the same symmetry on both: the images are equal where the boards are, word by word
+        for (uint32_t w = 0; w < BW; ++w) if (a[w] != b[w]) return false;
+        return true;
+    }
+    const uint8_t* pa = reinterpret_cast<const uint8_t*>(a); const uint8_t* pb = reinterpret_cast<const uint8_t*>(b);
+    const uint32_t ia = pooldd_sym_inverse(canon_a), ib = pooldd_sym_inverse(canon_b);
+    for (uint32_t r = 0; r < n; ++r)
+        for (uint32_t c = 0; c < n; ++c)
+            if (pa[pooldd_sym_rc(ia, r, c, n)] != pb[pooldd_sym_rc(ib, r, c, n)]) return false;
+    return true;
+}
+// where the probe of a key starts (a multiplicative hash, mapped to [0, TS) by the high half of a product: any TS) and goes on
+static TAFL_HD uint32_t pooldd_start(uint64_t key, uint32_t TS) { return (uint32_t)pool_mulhi64(key * 0x9E3779B97F4A7C15ull, (uint64_t)TS); }
+static TAFL_HD uint32_t pooldd_next(uint32_t pos, uint32_t TS) { return pos + 1u == TS ? 0u : pos + 1u; }
+// `cnt` rows of the key, `wins` / `losses` of them won / lost, the newest of age rank `age`, join the key's entry; returns the entry.  The
+// entry is found or claimed by linear probing (a free entry is claimed with a 64-bit compare-and-swap); all that is stored are sums and a
+// maximum of integers.  The table has more entries than keys, so the probe ends; it is bounded by TS all the same.
+static TAFL_HD uint32_t pooldd_insert(const PoolDedupTable& T, uint64_t key, uint32_t cnt, uint32_t wins, uint32_t losses, uint32_t age) {
+    uint32_t pos = pooldd_start(key, T.TS);
+    for (uint32_t i = 0; i < T.TS; ++i) {
+        unsigned long long k = T.key[pos];
+        if (k == 0ull) k = TAFL_POOLDD_CAS(&T.key[pos], 0ull, key);
+        if (k == 0ull || k == key) break;
+        pos = pooldd_next(pos, T.TS);
+    }
+    TAFL_POOLDD_ADD(&T.count[pos], cnt);
+    if (wins) TAFL_POOLDD_ADD(&T.wins[pos], wins);
+    if (losses) TAFL_POOLDD_ADD(&T.losses[pos], losses);
+    TAFL_POOLDD_MAX(&T.newest[pos], age);
+    return pos;
+}
+// the mean result of a group of m rows: integer counts and one division
+static TAFL_HD float pooldd_zmean(uint32_t m, uint32_t wins, uint32_t losses) {
+    return (float)(((double)wins - (double)losses + (double)(m - wins - losses) * (double)(float)TAFL_DRAW_VALUE) / (double)m);
+}
+// the weight tafl_pool_weights_from_dedup assigns to a live slot: w = its weight now, m = mult, is_rep = it is its group's representative
+static TAFL_HD uint32_t pooldd_weight(uint32_t w, uint32_t m, bool is_rep, uint32_t scale, uint32_t flags) {
+    if (m == 0u) m = 1u;                                                        // (no live slot of a valid result has it)
+    if (flags & 2u) return is_rep ? scale : 0u;
+    if (flags & 1u) { if (w == 0u) return 0u; const uint32_t q = w / m; return q ? q : 1u; }
+    const uint32_t q = scale / m;
+    return q ? q : 1u;
 }
 
 // The host's bookkeeping of a pool (tafl_pool_ingest, tafl_pool_trim, tafl_pool_get_stats): the live rows are [written - live, written),

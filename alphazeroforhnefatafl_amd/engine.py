@@ -13,7 +13,7 @@ import weakref
 
 from . import abi
 from ._lib import check, lib
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolIngestResult, TaflPoolStats, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflRootNoise, TaflMctsParams, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolDedupResult, TaflPoolIngestResult, TaflPoolStats, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflSolver, TaflSolverStats,
                   TaflSelfplayOpts, TaflState)
 
 
@@ -956,6 +956,51 @@ class Pool:
         assignment on the device, nothing is read back.  Needs weighting and search statistics on."""
         cfg = abi.TaflPoolSurpriseWeights(base=base, generation=generation, per_nat=per_nat)
         check(lib().tafl_pool_weights_from_surprise(self._h, C.byref(cfg)))
+        self.logic.sync()
+
+    # ---- de-duplication of positions (tafl_pool_dedup / _gather_dedup / _weights_from_dedup) ----
+    def dedup(self, symmetries: bool = False, key_bits: int = 64) -> TaflPoolDedupResult:
+        """Groups the live rows by position (side to move and board; symmetries: images under the eight board symmetries are one
+        position) and keeps, per live slot, the slot of the group's newest row, the group's size and its mean result.  Returns live,
+        distinct, largest, collisions, device_bytes.  The result stands until the next ingest, trim or clear.  key_bits below 64 makes
+        keys collide on purpose (tests, measuring collisions)."""
+        cfg = abi.TaflPoolDedupCfg(flags=abi.POOL_DEDUP_SYMMETRIES if symmetries else 0, key_bits=key_bits)
+        out = TaflPoolDedupResult()
+        check(lib().tafl_pool_dedup(self._h, C.byref(cfg), C.byref(out)))
+        return out
+
+    def free_dedup(self):
+        """Frees everything dedup allocated and drops its result."""
+        check(lib().tafl_pool_dedup(self._h, None, None))
+
+    def gather_dedup(self, slots, device: bool = False):
+        """(rep uint32 [k], mult uint32 [k], zmean float32 [k]) of the rows in `slots`.  device=False: a slot that is not live raises.
+        device=True: int32 tensor in, tensors out (rep and mult int32); a slot that is not live gives zeros and counts in stats().bad_slot."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            sl = self._device_u32(slots, "gather_dedup(device=True): slots")
+            k = int(sl.numel())
+            rep, mult = torch.empty((k,), dtype=torch.int32, device=sl.device), torch.empty((k,), dtype=torch.int32, device=sl.device)
+            zmean = torch.empty((k,), dtype=torch.float32, device=sl.device)
+            torch.cuda.current_stream(sl.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_gather_dedup(self._h, vp(sl.data_ptr()), k, vp(rep.data_ptr()), vp(mult.data_ptr()), vp(zmean.data_ptr()), 1))
+            self.logic.sync()
+            return rep, mult, zmean
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        k = int(sl.size)
+        rep, mult, zmean = np.zeros(k, np.uint32), np.zeros(k, np.uint32), np.zeros(k, np.float32)
+        check(lib().tafl_pool_gather_dedup(self._h, sl.ctypes.data_as(vp), k, rep.ctypes.data_as(vp), mult.ctypes.data_as(vp), zmean.ctypes.data_as(vp), 0))
+        return rep, mult, zmean
+
+    def weights_from_dedup(self, scale: int, divide: bool = False, representatives: bool = False):
+        """Every live row gets max(1, scale // mult) - every distinct position is then drawn equally often; divide: the weight it has
+        is divided by mult instead (0 stays 0, at least 1 otherwise); representatives: `scale` for the newest row of every group and 0
+        for the others.  An assignment on the device, nothing is read back.  Needs weighting on and a dedup result that stands."""
+        flags = (abi.POOL_DEDUP_DIVIDE if divide else 0) | (abi.POOL_DEDUP_REPRESENTATIVES if representatives else 0)
+        cfg = abi.TaflPoolDedupWeights(scale=scale, flags=flags)
+        check(lib().tafl_pool_weights_from_dedup(self._h, C.byref(cfg)))
         self.logic.sync()
 
     def weight_stats(self) -> TaflPoolWeightCounters:

@@ -1047,8 +1047,47 @@ int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device)
  *   which is an ASSIGNMENT, not the maximum rule of tafl_pool_set_weights; the other slots are unchanged.  One kernel over the slots on
  *   the context's stream, nothing is read back; the sums behind the weighted search are rebuilt by the next weighted sample, as after
  *   tafl_pool_set_weights.
+ * De-duplication of positions (nothing of it exists until the first tafl_pool_dedup; the rows of the ring are never moved or merged).
+ * tafl_pool_dedup(pool, cfg, out) groups the live rows [written - live, written) as they are at the call.  For a row with board bytes
+ *   b[t], t < n^2 (n = side_len) and side to move `side` (TAFL_ATTACKER / TAFL_DEFENDER as tafl_pool_gather writes it):
+ *     image(sigma)  has byte b[t] at tile sym_tile(sigma, t) (the symmetry of tafl_examples_gather), packed four tiles per 32-bit word -
+ *                   tile u is byte u & 3 of word u >> 2 - with zero bytes beyond n^2: BW = ceil(n^2 / 4) words w_0 .. w_{BW-1}
+ *     h(sigma)      x = 0x9E3779B97F4A7C15 ^ side;  for i = 0 .. BW-1: x = mix64(x ^ w_i)              (64-bit, wrapping)
+ *     mix64(x)      x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31   (the splitmix64 finaliser)
+ *     without TAFL_POOL_DEDUP_SYMMETRIES  key = h(0), canon = 0
+ *     with it                             key = min over sigma in 0..7 of h(sigma), canon = the smallest sigma that attains the minimum
+ *     then key &= 2^key_bits - 1 (cfg->key_bits in 1..64; 0 means 64), and a key of 0 becomes 1.
+ *   key_bits below 64 makes keys collide on purpose: it is how the colliding path is tested and how collisions can be measured.
+ *   Rows with equal keys form a group.  Of a group: m = its size; rep = the slot of its newest member (the largest age rank
+ *   (s - first + C) mod C, first = (written - live) mod C); wins / losses = its members with z == 1.0f / z == -1.0f;
+ *     zmean = (float)(((double)wins - (double)losses + (double)(m - wins - losses) * (double)(float)1e-4) / (double)m)
+ *   (1e-4 is z of a drawn game).  Kept beside the rows, per live slot s: rep[s], mult[s] = m, zmean[s].  They are pure functions of the
+ *   pool's contents: the groups are built from integer sums and maxima alone, no output depends on the order in which anything ran.
+ *   *out (may be NULL): live, distinct = the number of groups, largest = the largest m, collisions = the live rows whose side or canonical
+ *   image (the image under their own canon) differs from their representative's - expected to be 0 at 64 bits, a caller can check it -
+ *   and device_bytes = what de-duplication added to tafl_pool_stats.device_bytes.  The buffers are allocated by the first call and sized
+ *   for the capacity C: 25 * C bytes (rep, mult, zmean, the index of the row's table entry: 4 each; key: 8; canon: 1), a table of 24 bytes
+ *   per entry with TS(C) entries, TS(x) = the power of two >= max(64, 2 * x), 32 bytes of results, and the staging of host-pointer
+ *   tafl_pool_gather_dedup calls (16 bytes per row).  A call clears and uses TS(live) entries.  One 32-byte read-back per call.
+ *   Errors: unknown flag bits, key_bits > 64 or reserved words not 0: TAFL_ERR_UNSUPPORTED; live == 0: TAFL_ERR_INVALID_ARG; a capacity
+ *   above 2^30: TAFL_ERR_UNSUPPORTED.  cfg == NULL frees everything de-duplication allocated (tafl_pool_stats.device_bytes is what it was
+ *   before the first call) and drops the result; *out is zeroed.
+ *   The result stands until the next tafl_pool_ingest, tafl_pool_trim or tafl_pool_clear (whatever they change); after one of those
+ *   tafl_pool_gather_dedup and tafl_pool_weights_from_dedup return TAFL_ERR_INVALID_ARG until the next tafl_pool_dedup.
+ * tafl_pool_gather_dedup: rep[i], mult[i], zmean[i] of the row in slot[i] (any output may be NULL), with the rules of
+ *   tafl_pool_gather_stats for slots that are not live: refused with host pointers before anything is written (TAFL_ERR_INVALID_ARG),
+ *   zeros and counted in tafl_pool_stats.bad_slot with device pointers.
+ * tafl_pool_weights_from_dedup(pool, cfg): needs weighting on and a result that stands (otherwise TAFL_ERR_INVALID_ARG); unknown flag
+ *   bits, both flags together or reserved words not 0: TAFL_ERR_UNSUPPORTED.  For every live slot s, an ASSIGNMENT as in
+ *   tafl_pool_weights_from_surprise (integer division):
+ *     flags == 0                            wt[s] = max(1, scale / mult[s])         every distinct position is drawn equally often
+ *     TAFL_POOL_DEDUP_DIVIDE                wt[s] = wt[s] == 0 ? 0 : max(1, wt[s] / mult[s])     keeps the weights, spreads them over the group
+ *     TAFL_POOL_DEDUP_REPRESENTATIVES       wt[s] = rep[s] == s ? scale : 0         the newest search's policy, to be trained with zmean
+ *   One kernel over the slots on the context's stream, nothing is read back; the sums behind the weighted search are rebuilt by the next
+ *   weighted sample.
  * Not offered: saving and loading a pool, sampling without replacement, float weights,
- *   de-duplication of positions, ingesting examples that are not final, a pool that spans devices, surprise over unvisited children,
+ *   merging the policies of a group into one row, removing duplicate rows from the ring, de-duplication at ingest, groups across pools
+ *   or devices, ingesting examples that are not final, a pool that spans devices, surprise over unvisited children,
  *   decay of weights by generation. */
 typedef struct tafl_pool tafl_pool;                 /* opaque, owned by the ctx's device */
 typedef struct tafl_pool_stats {
@@ -1107,6 +1146,30 @@ typedef struct tafl_pool_surprise_weights {
 int tafl_pool_set_search_stats(tafl_pool* pool, int on);                              /* 0: off (the default) */
 int tafl_pool_gather_stats(tafl_pool* pool, const uint32_t* slot, uint32_t count, float* value, float* surprise, int ptrs_are_device);
 int tafl_pool_weights_from_surprise(tafl_pool* pool, const tafl_pool_surprise_weights* cfg);
+#define TAFL_POOL_DEDUP_SYMMETRIES 0x1u        /* tafl_pool_dedup: positions that are images of each other under a board symmetry are one group */
+typedef struct tafl_pool_dedup_cfg {
+    uint32_t flags;            /* 0 or TAFL_POOL_DEDUP_SYMMETRIES */
+    uint32_t key_bits;         /* bits of the hash that make the key, 1..64; 0: 64 */
+    uint32_t _reserved[6];     /* 0 */
+} tafl_pool_dedup_cfg;                              /* 32 bytes */
+typedef struct tafl_pool_dedup_result {
+    uint64_t live;             /* the rows the call looked at */
+    uint64_t distinct;         /* groups */
+    uint64_t largest;          /* members of the largest group */
+    uint64_t collisions;       /* live rows whose side or canonical image differs from their representative's */
+    uint64_t device_bytes;     /* what de-duplication added to tafl_pool_stats.device_bytes */
+    uint64_t _reserved[3];
+} tafl_pool_dedup_result;                           /* 64 bytes */
+#define TAFL_POOL_DEDUP_DIVIDE 0x1u            /* tafl_pool_weights_from_dedup: divide the weight a row has by its group's size */
+#define TAFL_POOL_DEDUP_REPRESENTATIVES 0x2u   /* tafl_pool_weights_from_dedup: `scale` for the newest row of a group, 0 for the others */
+typedef struct tafl_pool_dedup_weights {
+    uint32_t scale;            /* the weight of a distinct position (flags 0) or of a representative */
+    uint32_t flags;            /* 0, TAFL_POOL_DEDUP_DIVIDE or TAFL_POOL_DEDUP_REPRESENTATIVES */
+    uint32_t _reserved[6];     /* 0 */
+} tafl_pool_dedup_weights;                          /* 32 bytes */
+int tafl_pool_dedup(tafl_pool* pool, const tafl_pool_dedup_cfg* cfg, tafl_pool_dedup_result* out);       /* cfg NULL: free */
+int tafl_pool_gather_dedup(tafl_pool* pool, const uint32_t* slot, uint32_t count, uint32_t* rep, uint32_t* mult, float* zmean, int ptrs_are_device);
+int tafl_pool_weights_from_dedup(tafl_pool* pool, const tafl_pool_dedup_weights* cfg);
 
 /* ---- replay buffer on disk: write_to_file, game/main.rs:86-132 ------------------------
  * Host-only, byte-exact text format of the reference: per record `side_len` lines of comma-separated matrix values, one line
