@@ -6,7 +6,7 @@ import os
 import subprocess
 
 from . import abi
-from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolDedupCfg, TaflPoolDedupResult, TaflPoolDedupWeights, TaflPoolIngestResult, TaflPoolStats, TaflPoolSurpriseWeights, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats,
+from .abi import (TaflEffects, TaflEpisodeOpts, TaflEpisodeStats, TaflEvalSymmetry, TaflExamplesStats, TaflForcedPlayouts, TaflForcedPlayoutsStats, TaflGmctsStats, TaflMatchIo, TaflMatchOpts, TaflMatchStats, TaflMctsParams, TaflSelfplayOpts, TaflMctsStats, TaflPlay, TaflPlayoutCap, TaflPlayoutCapStats, TaflPoolDedupCfg, TaflPoolDedupResult, TaflPoolDedupWeights, TaflPoolIngestResult, TaflPoolStats, TaflPoolSurpriseWeights, TaflPoolWeightCounters, TaflPoolWeights, TaflRolloutResult, TaflRootChild, TaflRootNoise, TaflRules, TaflSolver, TaflSolverStats, TaflValueTargetsCfg, TaflValueTargetsResult,
                   TaflState)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -118,6 +118,10 @@ SYMBOLS = [
     ("tafl_pool_set_search_stats", _i32, [_vp, _i32]),
     ("tafl_pool_gather_stats", _i32, [_vp, _vp, _u32, _vp, _vp, _i32]),
     ("tafl_pool_weights_from_surprise", _i32, [_vp, _P(TaflPoolSurpriseWeights)]),
+    ("tafl_examples_value_targets", _i32, [_vp, _P(TaflValueTargetsCfg), _P(TaflValueTargetsResult)]),
+    ("tafl_examples_gather_targets", _i32, [_vp, _vp, _u32, _vp, _vp, _vp, _i32]),
+    ("tafl_pool_set_value_targets", _i32, [_vp, _i32]),
+    ("tafl_pool_gather_targets", _i32, [_vp, _vp, _u32, _vp, _vp, _i32]),
     ("tafl_pool_dedup", _i32, [_vp, _P(TaflPoolDedupCfg), _P(TaflPoolDedupResult)]),
     ("tafl_pool_gather_dedup", _i32, [_vp, _vp, _u32, _vp, _vp, _vp, _i32]),
     ("tafl_pool_weights_from_dedup", _i32, [_vp, _P(TaflPoolDedupWeights)]),

@@ -274,7 +274,19 @@ class TaflPoolDedupWeights(C.Structure):
     _fields_ = [("scale", C.c_uint32), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 6)]
 
 
+class TaflValueTargetsCfg(C.Structure):
+    """tafl_value_targets_cfg: lambda and the flags of tafl_examples_value_targets."""
+    _fields_ = [("lam", C.c_double), ("flags", C.c_uint32), ("_reserved", C.c_uint32 * 5)]
+
+
+class TaflValueTargetsResult(C.Structure):
+    """tafl_value_targets_result: what one tafl_examples_value_targets counted."""
+    _fields_ = [("episodes_closed", C.c_uint64), ("episodes_unfinished", C.c_uint64), ("rows_with_target", C.c_uint64), ("rows_settled", C.c_uint64)]
+
+
 EXAMPLES_SEARCH_STATS = 0x1      # tafl_examples_create_ex flags: keep Qsa and Ps of every stored child
+EXAMPLES_VALUE_TARGETS = 0x2     # tafl_examples_create_ex flags: episode boundaries and a value target per example (needs the one above)
+VT_SETTLE_UNFINISHED = 0x1       # tafl_value_targets_cfg flags: unfinished episodes get z = the last search value and final = 2
 POOL_SAMPLE_SYM = 0x1            # tafl_pool_sample flags: draw one of the eight symmetries per row
 POOL_DEDUP_SYMMETRIES = 0x1      # tafl_pool_dedup flags: images of a position under the board symmetries are one group
 POOL_DEDUP_DIVIDE = 0x1          # tafl_pool_weights_from_dedup flags: divide the weight a row has by its group's size
@@ -288,7 +300,8 @@ EXPECTED_SIZES = {"tafl_rules": 32, "tafl_play": 4, "tafl_state": 104, "tafl_eff
                   "tafl_forced_playouts": 32, "tafl_forced_playouts_stats": 32, "tafl_solver": 32, "tafl_solver_stats": 64,
                   "tafl_eval_symmetry": 32,
                   "tafl_pool_stats": 64, "tafl_pool_ingest_result": 32, "tafl_pool_weights": 32, "tafl_pool_weight_counters": 64,
-                  "tafl_pool_surprise_weights": 32, "tafl_pool_dedup_cfg": 32, "tafl_pool_dedup_result": 64, "tafl_pool_dedup_weights": 32}
+                  "tafl_pool_surprise_weights": 32, "tafl_pool_dedup_cfg": 32, "tafl_pool_dedup_result": 64, "tafl_pool_dedup_weights": 32,
+                  "tafl_value_targets_cfg": 32, "tafl_value_targets_result": 32}
 for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_state", TaflState),
                     ("tafl_effects", TaflEffects), ("tafl_rollout_result", TaflRolloutResult),
                     ("tafl_root_child", TaflRootChild), ("tafl_mcts_params", TaflMctsParams),
@@ -302,7 +315,8 @@ for _name, _cls in [("tafl_rules", TaflRules), ("tafl_play", TaflPlay), ("tafl_s
                     ("tafl_pool_stats", TaflPoolStats), ("tafl_pool_ingest_result", TaflPoolIngestResult),
                     ("tafl_pool_weights", TaflPoolWeights), ("tafl_pool_weight_counters", TaflPoolWeightCounters),
                     ("tafl_pool_surprise_weights", TaflPoolSurpriseWeights), ("tafl_pool_dedup_cfg", TaflPoolDedupCfg),
-                    ("tafl_pool_dedup_result", TaflPoolDedupResult), ("tafl_pool_dedup_weights", TaflPoolDedupWeights)]:
+                    ("tafl_pool_dedup_result", TaflPoolDedupResult), ("tafl_pool_dedup_weights", TaflPoolDedupWeights),
+                    ("tafl_value_targets_cfg", TaflValueTargetsCfg), ("tafl_value_targets_result", TaflValueTargetsResult)]:
     assert C.sizeof(_cls) == EXPECTED_SIZES[_name], (_name, C.sizeof(_cls))
 
 

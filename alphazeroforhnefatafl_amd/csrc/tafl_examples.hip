@@ -73,6 +73,43 @@ __global__ __launch_bounds__(256) void k_examples_gather_stats(ExamplesMem X, Ex
     if (surprise) surprise[i] = s;
 }
 
+// tafl_examples_value_targets, pass 1: one lane per entry of the per-example arrays (consecutive g: a wave's loads of info, pol and cq
+// coalesce), the search value and the participation bit staged in vt and kind
+__global__ __launch_bounds__(256) void k_examples_vt_stage(ExamplesMem X, ExampleStatsMem S, ExampleTargetsMem T, uint32_t E) {
+    const unsigned long long e = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    if (e < E) vt_stage(X, S, T, (uint32_t)e);
+}
+// pass 2: one lane per game walks its examples backward (entries j * G + g: a wave's accesses coalesce), the whole wave as far as its
+// longest lane so that the four counters go through ballots; one flush per wave
+__global__ __launch_bounds__(TAFL_BLOCK) void k_examples_vt_chain(ExamplesMem X, ExampleTargetsMem T, double lambda, uint32_t settle, unsigned long long* res) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    const uint32_t len = g < X.G ? (X.len[g] < X.max_moves ? X.len[g] : X.max_moves) : 0u;
+    uint32_t top = len;
+    for (int d = 32; d >= 1; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)top, d, 64); top = o > top ? o : top; }
+    VtChain c; c.A = 0.0; c.L = 1.0; c.u_last = 0.0; c.u_next = 0.0; c.mv_next = 0u; c.have = 0u; c.closed = 0u;
+    uint32_t n[VT_COUNTERS] = {0u, 0u, 0u, 0u};
+    for (uint32_t j = top; j-- > 0u;) {
+        const uint32_t ev = j < len ? vt_step(X, T, j, g, lambda, settle != 0u, c) : 0u;
+        n[VT_ROWS] += (uint32_t)__popcll(__ballot(ev & VT_EV_ROW));
+        n[VT_CLOSED] += (uint32_t)__popcll(__ballot(ev & VT_EV_CLOSED));
+        n[VT_UNFINISHED] += (uint32_t)__popcll(__ballot(ev & VT_EV_UNFINISHED));
+        n[VT_SETTLED] += (uint32_t)__popcll(__ballot(ev & VT_EV_SETTLED));
+    }
+    if (threadIdx.x == 0)
+        for (uint32_t k = 0; k < VT_COUNTERS; ++k) if (n[k]) atomicAdd(&res[k], (unsigned long long)n[k]);
+}
+// tafl_examples_gather_targets, one lane per row: an index that names no example gives zeros and is counted
+__global__ __launch_bounds__(256) void k_examples_gather_targets(ExamplesMem X, ExampleTargetsMem T, const uint32_t* index, uint32_t count, float* target, uint8_t* kind, uint8_t* ep_end) {
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    if (i >= count) return;
+    const uint32_t e = index[i], g = e % X.G, j = e / X.G;
+    const bool ok = j < X.max_moves && j < X.len[g];
+    if (!ok) atomicAdd(&X.counters[EX_BAD_INDEX], 1ull);
+    if (target) target[i] = ok ? T.vt[e] : 0.0f;
+    if (kind) kind[i] = ok ? T.kind[e] : (uint8_t)0;
+    if (ep_end) ep_end[i] = ok ? T.ep_end[e] : (uint8_t)0;
+}
+
 #define EXCHK(ex, name) do { if (!(ex)) return fail(TAFL_ERR_INVALID_ARG, name ": null examples object"); HIPCHK(hipSetDevice((ex)->ctx->device)); } while (0)
 
 extern "C" {
@@ -81,7 +118,9 @@ int tafl_examples_create(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint
     return tafl_examples_create_ex(c, n_games, max_moves, max_children, 0u, out);
 }
 int tafl_examples_create_ex(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, uint32_t max_children, uint32_t flags, tafl_examples** out) {
-    if (flags & ~(uint32_t)TAFL_EXAMPLES_SEARCH_STATS) return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_create_ex: unknown flag bits");
+    if (flags & ~(uint32_t)(TAFL_EXAMPLES_SEARCH_STATS | TAFL_EXAMPLES_VALUE_TARGETS)) return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_create_ex: unknown flag bits");
+    if ((flags & TAFL_EXAMPLES_VALUE_TARGETS) && !(flags & TAFL_EXAMPLES_SEARCH_STATS))
+        return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_create_ex: TAFL_EXAMPLES_VALUE_TARGETS needs TAFL_EXAMPLES_SEARCH_STATS");
     if (!c || !out || n_games == 0 || max_moves == 0 || max_children == 0 || max_children > 0xFFFFu)
         return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: bad argument (n_games, max_moves >= 1, max_children in 1..65535)");
     if ((unsigned long long)n_games * max_moves > 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_create: n_games * max_moves exceeds 32 bits");
@@ -94,7 +133,8 @@ int tafl_examples_create_ex(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, u
     if (x->need(x->len, 4 * (size_t)n_games) || x->need(x->boards, 4 * E * BW) || x->need(x->info, 4 * E) || x->need(x->played, 4 * E) || x->need(x->move_no, 4 * E) ||
         x->need(x->pol, 4 * E * max_children) || x->need(x->z, 4 * E) || x->need(x->fin, E) || x->need(x->counters, 8 * EX_COUNTERS) ||
         x->need(x->open_from, 4 * (size_t)n_games) ||
-        ((flags & TAFL_EXAMPLES_SEARCH_STATS) && (x->need(x->cq, 4 * E * max_children) || x->need(x->cp, 4 * E * max_children) || x->need(x->seen, 4 * (size_t)n_games)))) {
+        ((flags & TAFL_EXAMPLES_SEARCH_STATS) && (x->need(x->cq, 4 * E * max_children) || x->need(x->cp, 4 * E * max_children) || x->need(x->seen, 4 * (size_t)n_games))) ||
+        ((flags & TAFL_EXAMPLES_VALUE_TARGETS) && (x->need(x->ep_end, E) || x->need(x->vt, 4 * E) || x->need(x->kind, E) || x->need(x->vt_res, 8 * VT_COUNTERS)))) {
         tafl_examples_destroy(x);
         return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_examples_create)");
     }
@@ -102,6 +142,7 @@ int tafl_examples_create_ex(tafl_ctx* c, uint32_t n_games, uint32_t max_moves, u
     x->len.bind(M.len); x->boards.bind(M.boards); x->info.bind(M.info); x->played.bind(M.played); x->move_no.bind(M.move_no);
     x->pol.bind(M.pol); x->z.bind(M.z); x->fin.bind(M.fin); x->counters.bind(M.counters);
     if (flags & TAFL_EXAMPLES_SEARCH_STATS) { x->cq.bind(x->smem.cq); x->cp.bind(x->smem.cp); x->seen.bind(x->smem.seen); }
+    if (flags & TAFL_EXAMPLES_VALUE_TARGETS) { x->ep_end.bind(x->tmem.ep_end); x->vt.bind(x->tmem.vt); x->kind.bind(x->tmem.kind); }
     M.G = n_games; M.max_moves = max_moves; M.K = max_children; M.BW = (uint32_t)BW;
     const int rc = tafl_examples_clear(x);
     if (rc) { tafl_examples_destroy(x); return rc; }
@@ -123,6 +164,11 @@ int tafl_examples_clear(tafl_examples* x) {
     HIPCHK(hipMemsetAsync(x->counters.p, 0, 8 * EX_COUNTERS, s));
     HIPCHK(hipMemsetAsync(x->open_from.p, 0, 4 * (size_t)x->n_games, s));
     if (x->seen.p) HIPCHK(hipMemsetAsync(x->seen.p, 0, 4 * (size_t)x->n_games, s));
+    if (x->ep_end.p) {                                       // no boundary is known any more; vt and kind never hold anything but zeros or a result
+        const size_t E = (size_t)x->n_games * x->max_moves;
+        HIPCHK(hipMemsetAsync(x->ep_end.p, 0, E, s)); HIPCHK(hipMemsetAsync(x->vt.p, 0, 4 * E, s)); HIPCHK(hipMemsetAsync(x->kind.p, 0, E, s));
+    }
+    x->vt_valid = false;
     return sync_ok(x->ctx);
 }
 int tafl_examples_counts(tafl_examples* x, uint32_t* out_len, uint64_t* out_total) {
@@ -175,6 +221,7 @@ int tafl_examples_finalize(tafl_examples* x, tafl_batch* b) {
     if (const int rc = join_search(b)) return rc;
     tafl_ctx* c = b->ctx;
     if (c != x->ctx) HIPCHK(hipStreamSynchronize(x->ctx->stream));
+    x->vt_valid = false;                                     // (z and final of the open tail change: the targets are stale)
     dispatch<BATCH, false>(c, [&](auto t) { LAUNCH_PER_GAME((k_examples_finalize<t.NL>), c, b->n, b->soa, x->mem, x->open_from.as<const uint32_t>()); });
     HIPCHK(hipGetLastError());
     return sync_ok(c);
@@ -332,6 +379,65 @@ int tafl_examples_gather_stats(tafl_examples* x, const uint32_t* index, uint32_t
     HIPCHK(hipGetLastError());
     COPY_OUT(value, x->g_z.p, count, s);
     COPY_OUT(surprise, x->g_s.p, count, s);
+    HIPCHK(hipStreamSynchronize(s));
+    return TAFL_OK;
+}
+
+// the two passes of the value targets (include/taflhip.h): asynchronous up to the 32-byte read-back of the counters
+int tafl_examples_value_targets(tafl_examples* x, const tafl_value_targets_cfg* cfg, tafl_value_targets_result* out) {
+    EXCHK(x, "tafl_examples_value_targets");
+    if (!cfg) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_value_targets: null argument");
+    if (!(x->flags & TAFL_EXAMPLES_VALUE_TARGETS)) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_value_targets: the object was created without TAFL_EXAMPLES_VALUE_TARGETS");
+    if (!(cfg->lambda >= 0.0 && cfg->lambda <= 1.0)) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_value_targets: lambda must be in [0, 1]");
+    if (cfg->flags & ~(uint32_t)TAFL_VT_SETTLE_UNFINISHED) return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_value_targets: unknown flag bits");
+    for (uint32_t r : cfg->_reserved) if (r) return fail(TAFL_ERR_UNSUPPORTED, "tafl_examples_value_targets: reserved words must be 0");
+    hipStream_t s = x->ctx->stream;
+    const uint32_t E = x->n_games * x->max_moves;
+    unsigned long long* res = x->vt_res.as<unsigned long long>();
+    x->vt_valid = false;
+    HIPCHK(hipMemsetAsync(res, 0, 8 * VT_COUNTERS, s));
+    hipLaunchKernelGGL(k_examples_vt_stage, dim3((uint32_t)(((unsigned long long)E + 255u) / 256u)), dim3(256), 0, s, x->mem, x->smem, x->tmem, E);
+    hipLaunchKernelGGL(k_examples_vt_chain, dim3(grid_of(x->n_games)), dim3(TAFL_BLOCK), 0, s, x->mem, x->tmem, cfg->lambda, cfg->flags & (uint32_t)TAFL_VT_SETTLE_UNFINISHED, res);
+    HIPCHK(hipGetLastError());
+    unsigned long long h[VT_COUNTERS];
+    HIPCHK(hipMemcpyAsync(h, res, sizeof h, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    x->vt_valid = true;
+    if (out) { out->episodes_closed = h[VT_CLOSED]; out->episodes_unfinished = h[VT_UNFINISHED]; out->rows_with_target = h[VT_ROWS]; out->rows_settled = h[VT_SETTLED]; }
+    return TAFL_OK;
+}
+
+// vt, kind and ep_end per row: with device pointers one asynchronous launch, a bad index gives zeros and is counted
+int tafl_examples_gather_targets(tafl_examples* x, const uint32_t* index, uint32_t count, float* target, uint8_t* kind, uint8_t* ep_end, int ptrs_are_device) {
+    EXCHK(x, "tafl_examples_gather_targets");
+    if (!(x->flags & TAFL_EXAMPLES_VALUE_TARGETS)) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_targets: the object was created without TAFL_EXAMPLES_VALUE_TARGETS");
+    if ((target || kind) && !x->vt_valid) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_targets: the targets are stale (tafl_examples_value_targets has not run since the last clear, finalize or run)");
+    if (!index && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_targets: null index");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = x->ctx->stream;
+    const uint32_t grid = (uint32_t)(((unsigned long long)count + 255u) / 256u);
+    if (ptrs_are_device) {
+        hipLaunchKernelGGL(k_examples_gather_targets, dim3(grid), dim3(256), 0, s, x->mem, x->tmem, index, count, target, kind, ep_end);
+        HIPCHK(hipGetLastError());
+        return TAFL_OK;
+    }
+    {
+        std::vector<uint32_t> len(x->n_games);
+        COPY_OUT(len.data(), x->len.p, x->n_games, s);
+        HIPCHK(hipStreamSynchronize(s));
+        for (uint32_t i = 0; i < count; ++i) {
+            const uint32_t g = index[i] % x->n_games, j = index[i] / x->n_games;
+            if (j >= x->max_moves || j >= len[g]) return fail(TAFL_ERR_INVALID_ARG, "tafl_examples_gather_targets: index " + std::to_string(index[i]) + " (row " + std::to_string(i) + ") names no recorded example");
+        }
+    }
+    EXNEED(x->g_index, 4 * (size_t)count); EXNEED(x->g_z, 4 * (size_t)count); EXNEED(x->g_fin, count); EXNEED(x->g_k, count);
+    HIPCHK(hipMemcpyAsync(x->g_index.p, index, 4 * (size_t)count, hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(k_examples_gather_targets, dim3(grid), dim3(256), 0, s, x->mem, x->tmem, x->g_index.as<const uint32_t>(), count, target ? x->g_z.as<float>() : nullptr,
+                       kind ? x->g_fin.as<uint8_t>() : nullptr, ep_end ? x->g_k.as<uint8_t>() : nullptr);
+    HIPCHK(hipGetLastError());
+    COPY_OUT(target, x->g_z.p, count, s);
+    COPY_OUT(kind, x->g_fin.p, count, s);
+    COPY_OUT(ep_end, x->g_k.p, count, s);
     HIPCHK(hipStreamSynchronize(s));
     return TAFL_OK;
 }

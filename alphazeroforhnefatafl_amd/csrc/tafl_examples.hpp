@@ -112,6 +112,78 @@ static TAFL_HD void example_search_stats(const ExamplesMem& X, const ExampleStat
     surprise = (float)(s > 0.0 ? s : 0.0);
 }
 
+// ---- value targets from search values (include/taflhip.h TAFL_EXAMPLES_VALUE_TARGETS; the text there is normative) ----
+// The arrays of an object created with the flag, a struct of its own for the reason ExampleStatsMem is one.
+struct ExampleTargetsMem {
+    uint8_t* ep_end;             // [e] 1: the example is the last of its lane's episode (vt_mark_boundary)
+    float* vt;                   // [e] the target (between the two passes of tafl_examples_value_targets: the example's search value)
+    uint8_t* kind;               // [e] 0 no target, 1 from a closed episode, 2 from an unfinished one (between the passes: 1 = takes part)
+};
+enum { VT_CLOSED = 0, VT_UNFINISHED = 1, VT_ROWS = 2, VT_SETTLED = 3, VT_COUNTERS = 4 };
+// The boundary recorder, for game g at the begin of a run and after every round and its reopen: the value open_from[g] holds marks the
+// example before it.  Stateless, so a value that stands for many rounds, or that a reopen without a new example repeats, marks once.
+static TAFL_HD void vt_mark_boundary(const ExamplesMem& X, const ExampleTargetsMem& T, const uint32_t* open_from, uint32_t g) {
+    const uint32_t o = open_from[g];
+    if (o == 0u || o > X.len[g] || o > X.max_moves) return;
+    const size_t e = (size_t)(o - 1u) * X.G + g;
+    if (!T.ep_end[e]) T.ep_end[e] = 1;
+}
+// value of example_search_stats alone (the same operations, hence the same bits); false: N == 0, the example takes no part
+static TAFL_HD bool example_search_value(const ExamplesMem& X, const ExampleStatsMem& S, uint32_t j, uint32_t g, uint32_t info, float& value) {
+    const uint32_t nc = example_stored_children(X, info);
+    value = 0.0f;
+    uint32_t N = 0;
+    for (uint32_t k = 0; k < nc; ++k) N += X.pol[((size_t)j * X.K + k) * X.G + g] >> 16;
+    if (N == 0u) return false;
+    double acc = 0.0;
+    for (uint32_t k = 0; k < nc; ++k) {
+        const size_t at = ((size_t)j * X.K + k) * X.G + g;
+        acc = acc + (double)(X.pol[at] >> 16) * (double)S.cq[at];
+    }
+    value = (float)(acc / (double)N);
+    return true;
+}
+// pass 1, entry e of the per-example arrays: the search value and the participation bit are staged in vt and kind
+static TAFL_HD void vt_stage(const ExamplesMem& X, const ExampleStatsMem& S, const ExampleTargetsMem& T, uint32_t e) {
+    const uint32_t g = e % X.G, j = e / X.G;
+    if (j >= X.max_moves || j >= X.len[g]) return;
+    float v;
+    const bool part = example_search_value(X, S, j, g, X.info[e], v);
+    T.vt[e] = v; T.kind[e] = part ? 1 : 0;
+}
+static TAFL_HD double vt_lam_pow(double lambda, uint32_t d) {
+    double r = 1.0, b = lambda;
+    for (uint32_t bit = 0; bit < 16u; ++bit) { if ((d >> bit) & 1u) r = r * b; b = b * b; }
+    return r;
+}
+// pass 2, one lane per game walks its examples backward; what it carries from example j + 1 to example j
+struct VtChain { double A, L, u_last, u_next; uint32_t mv_next, have, closed; };
+enum { VT_EV_ROW = 1u, VT_EV_CLOSED = 2u, VT_EV_UNFINISHED = 4u, VT_EV_SETTLED = 8u };
+// example (j, g) of the backward walk: writes vt and kind (and z, fin when an unfinished episode is settled); returns what to count
+static TAFL_HD uint32_t vt_step(const ExamplesMem& X, const ExampleTargetsMem& T, uint32_t j, uint32_t g, double lambda, bool settle, VtChain& c) {
+    const size_t e = (size_t)j * X.G + g;
+    if (T.ep_end[e]) c.have = 0u;                                  // the last example of an episode: nothing follows it in the chain
+    if (!T.kind[e]) { T.vt[e] = 0.0f; return 0u; }
+    const double s = ((X.info[e] >> 16) & 0xFFu) == (uint32_t)TAFL_ATTACKER ? 1.0 : -1.0, u = s * (double)T.vt[e];
+    const uint32_t mv = X.move_no[e];
+    uint32_t ev = VT_EV_ROW;
+    if (!c.have) {
+        c.have = 1u; c.closed = X.fin[e] == 1 ? 1u : 0u; c.A = 0.0; c.L = 1.0; c.u_last = u;
+        ev |= c.closed ? VT_EV_CLOSED : VT_EV_UNFINISHED;
+    } else {
+        uint32_t d = c.mv_next > mv ? c.mv_next - mv : 1u;
+        if (d > 65535u) d = 65535u;
+        const double p = vt_lam_pow(lambda, d);
+        c.A = (1.0 - p) * c.u_next + p * c.A;
+        c.L = p * c.L;
+    }
+    c.u_next = u; c.mv_next = mv;
+    const double term = c.closed ? (double)X.z[e] : s * c.u_last;
+    T.vt[e] = (float)(s * c.A + c.L * term); T.kind[e] = c.closed ? 1 : 2;
+    if (!c.closed && settle) { X.z[e] = (float)(s * c.u_last); X.fin[e] = 2; ev |= VT_EV_SETTLED; }
+    return ev;
+}
+
 // The entry a move is drawn with, among n entries of which entry j has count(j) visits: k = mulhi(r, N) = (r * N) >> 32 with N = the sum of
 // the counts, and the draw is the first entry in canonical (= ascending action) order whose running sum exceeds k: entry j is drawn for
 // floor-exact count(j) / N of the 2^32 values of r.  Integers only.  Entries without visits (the unvisited edges of a guided root) add

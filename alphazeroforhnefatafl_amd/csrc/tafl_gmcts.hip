@@ -585,6 +585,7 @@ int tafl_gmcts_begin_ex(tafl_batch* b, uint32_t max_sims, uint32_t edges_per_nod
     if ((flags & TAFL_GMCTS_KEEP_TREE) && b->noise_set) return fail(TAFL_ERR_UNSUPPORTED, "tafl_gmcts_begin_ex: root noise on a retained tree is not supported (tafl_gmcts_set_root_noise(NULL) first)");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     b->gsp_active = false;                                   // (a guided self-play run on this arena is closed)
+    b->gsp_targets = ExampleTargetsMem{}; b->gsp_open_from = nullptr; b->gsp_targets_ex = nullptr;      // (the closed run holds its examples object no longer)
     b->g_noise_on = b->noise_set;                            // the search latches the noise setting
     if (b->noise_set) b->g_noise = noise_arg(b->noise_cfg);
     HIPCHK(hipSetDevice(c->device));
@@ -685,6 +686,7 @@ int tafl_gmcts_advance(tafl_batch* b, const uint32_t* actions, tafl_play* out_pl
     if (!b || !b->g_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: tafl_gmcts_begin first");
     if (const int rc = join_search(b)) return rc;
     b->gsp_active = false;
+    b->gsp_targets = ExampleTargetsMem{}; b->gsp_open_from = nullptr; b->gsp_targets_ex = nullptr;      // (the closed run holds its examples object no longer)
     const bool live = b->g_tree_live;
     if (!actions && !live) return fail(TAFL_ERR_INVALID_ARG, "tafl_gmcts_advance: actions == NULL needs a retained tree");
     tafl_ctx* c = b->ctx;
@@ -728,11 +730,25 @@ __global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_record_stats(GuidedMem
     if (g >= M.G) return;
     record_stats(M, g, X, S);
 }
+// the recorder of episode boundaries (vt_mark_boundary): one lane per game, behind the recorder above, hence after
+// the reopen of every family; launched only for a run whose examples object carries value targets
+__global__ __launch_bounds__(TAFL_BLOCK) void k_gselfplay_mark_boundary(ExamplesMem X, ExampleTargetsMem T, const uint32_t* open_from) {
+    const uint32_t g = blockIdx.x * TAFL_BLOCK + threadIdx.x;
+    if (g >= X.G) return;
+    vt_mark_boundary(X, T, open_from, g);
+}
+static int gselfplay_mark_boundary(tafl_batch* b) {
+    if (!b->gsp_targets.ep_end) return TAFL_OK;
+    b->gsp_targets_ex->vt_valid = false;                     // (a round may append examples the targets know nothing of)
+    LAUNCH_PER_GAME(k_gselfplay_mark_boundary, b->ctx, b->n, b->gsp_rec.ex, b->gsp_targets, b->gsp_open_from);
+    HIPCHK(hipGetLastError());
+    return TAFL_OK;
+}
 static int gselfplay_record_stats(tafl_batch* b) {
     if (!b->gsp_stats.cq) return TAFL_OK;
     LAUNCH_PER_GAME(k_gselfplay_record_stats, b->ctx, b->n, b->gmem, b->gsp_rec.ex, b->gsp_stats);
     HIPCHK(hipGetLastError());
-    return TAFL_OK;
+    return gselfplay_mark_boundary(b);
 }
 static int gselfplay_rounds(tafl_batch* b, const float* dp, const float* dv);
 static int gselfplay_launch(tafl_batch* b, const float* dp, const float* dv) {
@@ -842,6 +858,11 @@ static int gselfplay_begin(tafl_batch* b, uint32_t n_sims, uint32_t edges_per_no
         b->gsp_stats = ex->smem;
         HIPCHK(hipMemcpyAsync(ex->seen.p, ex->len.p, sizeof(uint32_t) * (size_t)n, hipMemcpyDeviceToDevice, c->stream));
     }
+    b->gsp_targets = ExampleTargetsMem{}; b->gsp_open_from = nullptr; b->gsp_targets_ex = nullptr;
+    if (ex && (ex->flags & TAFL_EXAMPLES_VALUE_TARGETS)) {     // the boundary the object's open_from names as the run begins; its targets are stale from here on
+        b->gsp_targets = ex->tmem; b->gsp_open_from = ex->open_from.as<const uint32_t>(); b->gsp_targets_ex = ex;
+        if (const int rc = gselfplay_mark_boundary(b)) return rc;
+    }
     b->gsp_rec.sample_seed = o->sample_seed; b->gsp_rec.game_id_base = game_id_base; b->gsp_rec.temp_moves = o->temp_moves; b->gsp_rec.move_base = o->move_base;
     b->gsp_sims = n_sims; b->gsp_cpuct = c_puct;
     b->g_noise_on = b->noise_set;                            // the run latches the noise setting; gid and M are the run's own
@@ -916,6 +937,7 @@ int tafl_gselfplay_end(tafl_batch* b, tafl_play* out_plays, uint32_t* out_moves)
     if (!b || !b->gsp_has) return fail(TAFL_ERR_INVALID_ARG, "tafl_gselfplay_end: tafl_gselfplay_begin first");
     tafl_ctx* c = b->ctx; const uint32_t n = b->n;
     b->gsp_active = false;
+    b->gsp_targets = ExampleTargetsMem{}; b->gsp_open_from = nullptr; b->gsp_targets_ex = nullptr;      // (the closed run holds its examples object no longer)
     HIPCHK(hipSetDevice(c->device));
     COPY_OUT(out_plays, b->gsp_plays.p, (size_t)n * b->gsp.n_moves, c->stream);
     COPY_OUT(out_moves, b->gsp_moves_done.p, n, c->stream);

@@ -226,6 +226,9 @@ struct tafl_batch {
     bool gsp_active = false, gsp_first = false, gsp_has = false;
     GSelfPlay gsp = {}; SelfPlayRec gsp_rec = {}; uint32_t gsp_sims = 0; double gsp_cpuct = 0.0;
     ExampleStatsMem gsp_stats = {};  // the run records into an examples object with search statistics (cq != nullptr): k_gselfplay_record_stats follows every round
+    // ... and value targets (ep_end != nullptr): k_gselfplay_mark_boundary follows the recorder, reading the object's open_from
+    ExampleTargetsMem gsp_targets = {}; const uint32_t* gsp_open_from = nullptr;
+    struct tafl_examples* gsp_targets_ex = nullptr;      // that object: every round of the run marks its targets stale
     DevBuf gsp_moves_done, gsp_plays;
     // an episodes run (tafl_gselfplay_begin_episodes): per lane the episode number and the move count at which it began, the openings
     // (quad-plane SoA like the batch states) and the four result counters; gsp_episodes: the run that is open, or was last, is one
@@ -274,6 +277,11 @@ struct tafl_examples {
     ExampleStatsMem smem = {};       // TAFL_EXAMPLES_SEARCH_STATS: the arrays beside pol (all null without the flag)
     DevBuf len, boards, info, played, move_no, pol, z, fin, counters;
     DevBuf cq, cp, seen, g_s;        // g_s: staging of the second scalar of a host-pointer tafl_examples_gather_stats
+    // TAFL_EXAMPLES_VALUE_TARGETS: the three arrays (all null without the flag), the four result counters, the staging of the second byte
+    // of a host-pointer tafl_examples_gather_targets; vt_valid: a result of tafl_examples_value_targets stands
+    ExampleTargetsMem tmem = {};
+    DevBuf ep_end, vt, kind, vt_res, g_k;
+    bool vt_valid = false;
     DevBuf open_from;                // [n_games] first example of game g whose result is still open: 0 unless an episodes run has moved it
     DevBuf g_index, g_sym, g_boards, g_sides, g_pi, g_z, g_fin;      // staging of a gather with host pointers
     size_t device_bytes = 0;         // sum of the capacities above: every allocation goes through need()

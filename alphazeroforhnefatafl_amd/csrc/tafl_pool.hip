@@ -117,6 +117,30 @@ __global__ __launch_bounds__(POOL_TILE) void k_pool_ingest_stats(ExamplesMem X, 
     const uint32_t slot = pool_stored_slot(written, rank - first, T, C);
     value[slot] = v; surprise[slot] = s;
 }
+// Ingest, the pass of a pool that carries value targets (tafl_pool_set_value_targets): the rank and the placement of k_pool_ingest_stats,
+// vt and kind of a stored example copied to its slot
+__global__ __launch_bounds__(POOL_TILE) void k_pool_ingest_targets(ExamplesMem X, ExampleTargetsMem T, uint32_t E, const uint32_t* prefix, const unsigned long long* res,
+                                                                   unsigned long long written, uint32_t C, float* vt, uint8_t* kind) {
+    __shared__ uint32_t wave_tot[POOL_TILE / 64];
+    uint32_t info, e, lr, nt;
+    const bool taken = pool_tile_flags(X, E, wave_tot, info, e, lr, nt) == POOL_TAKEN;
+    if (!taken) return;
+    const uint32_t Tn = (uint32_t)res[0], rank = prefix[blockIdx.x] + lr, first = Tn - (Tn < C ? Tn : C);
+    if (rank < first) return;
+    const uint32_t slot = pool_stored_slot(written, rank - first, Tn, C);
+    vt[slot] = T.vt[e]; kind[slot] = T.kind[e];
+}
+// tafl_pool_gather_targets: zeros for a slot that is not live, counted
+__global__ __launch_bounds__(256) void k_pool_gather_targets(const float* tv, const uint8_t* tk, unsigned long long* counters, const uint32_t* slot, uint32_t count, uint32_t first,
+                                                             unsigned long long live, uint32_t C, float* target, uint8_t* kind) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < count; i += (unsigned long long)gridDim.x * 256) {
+        const uint32_t s = slot[i];
+        const bool ok = pool_slot_live_from(s, first, live, C);
+        if (!ok) atomicAdd(&counters[POOL_BAD_SLOT], 1ull);
+        if (target) target[i] = ok ? tv[s] : 0.0f;
+        if (kind) kind[i] = ok ? tk[s] : (uint8_t)0;
+    }
+}
 // tafl_pool_gather_stats: zeros for a slot that is not live, counted
 __global__ __launch_bounds__(256) void k_pool_gather_stats(const float* sv, const float* ss, unsigned long long* counters, const uint32_t* slot, uint32_t count, uint32_t first,
                                                            unsigned long long live, uint32_t C, float* value, float* surprise) {
@@ -446,6 +470,9 @@ struct tafl_pool {
     // search statistics per row (tafl_pool_set_search_stats; off: no buffer of it exists): value and surprise of the row in slot s
     bool search_stats = false;
     DevBuf s_value, s_surprise, g_s;     // g_s: staging of the second scalar of a host-pointer tafl_pool_gather_stats
+    // value targets per row (tafl_pool_set_value_targets; off: no buffer of it exists): vt and kind of the row in slot s
+    bool value_targets = false;
+    DevBuf t_vt, t_kind, g_k;            // g_k: staging of the kinds of a host-pointer tafl_pool_gather_targets
     // de-duplication (tafl_pool_dedup; before the first call and after tafl_pool_dedup(pool, NULL, ..): no buffer of it exists)
     bool dd_valid = false;               // a result stands: no ingest, trim or clear since the last tafl_pool_dedup
     DevBuf dd_rep, dd_mult, dd_zmean, dd_canon, dd_key, dd_ent, dd_table, dd_res, dd_stage;     // dd_stage: slot, rep, mult, zmean of a host-pointer gather
@@ -568,6 +595,8 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     if (p->book.ingests >= 0xFFFFFFFFull) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the generation exceeds 32 bits");
     if (p->search_stats && !(ex->flags & TAFL_EXAMPLES_SEARCH_STATS))
         return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the pool carries search statistics, the examples object was created without TAFL_EXAMPLES_SEARCH_STATS");
+    if (p->value_targets && !((ex->flags & TAFL_EXAMPLES_VALUE_TARGETS) && ex->vt_valid))
+        return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_ingest: the pool carries value targets, the examples object was created without TAFL_EXAMPLES_VALUE_TARGETS or its targets are stale");
     tafl_ctx* c = p->ctx; hipStream_t s = c->stream;
     p->dd_valid = false;
     const uint32_t E = ex->n_games * ex->max_moves, nb = (uint32_t)(((unsigned long long)E + POOL_TILE - 1) / POOL_TILE);       // (E fits 32 bits: tafl_examples_create)
@@ -582,6 +611,9 @@ int tafl_pool_ingest(tafl_pool* p, tafl_examples* ex, tafl_pool_ingest_result* o
     if (p->search_stats)
         hipLaunchKernelGGL(k_pool_ingest_stats, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, ex->smem, E, (const uint32_t*)prefix, (const unsigned long long*)res,
                            (unsigned long long)p->book.written, p->mem.C, p->s_value.as<float>(), p->s_surprise.as<float>());
+    if (p->value_targets)
+        hipLaunchKernelGGL(k_pool_ingest_targets, dim3(nb), dim3(POOL_TILE), 0, s, ex->mem, ex->tmem, E, (const uint32_t*)prefix, (const unsigned long long*)res,
+                           (unsigned long long)p->book.written, p->mem.C, p->t_vt.as<float>(), p->t_kind.as<uint8_t>());
     if (p->weighting) {
         const uint32_t most = E < p->mem.C ? E : p->mem.C, grid = std::min<uint32_t>((most + 255u) / 256u, 2048u);       // (T <= E rows at most)
         if (grid) hipLaunchKernelGGL(k_poolw_ingest, dim3(grid), dim3(256), 0, s, p->wmem.wt, (const unsigned long long*)res, (unsigned long long)p->book.written, p->mem.C, p->ingest_weight);
@@ -817,8 +849,8 @@ int tafl_pool_set_search_stats(tafl_pool* p, int on) {
     hipStream_t s = p->ctx->stream;
     if (!on) {
         HIPCHK(hipStreamSynchronize(s));
-        for (DevBuf* d : {&p->s_value, &p->s_surprise, &p->g_s}) { p->device_bytes -= d->cap; d->release(); }
-        p->search_stats = false;
+        for (DevBuf* d : {&p->s_value, &p->s_surprise, &p->g_s, &p->t_vt, &p->t_kind, &p->g_k}) { p->device_bytes -= d->cap; d->release(); }
+        p->search_stats = false; p->value_targets = false;      // (value targets need the statistics)
         return TAFL_OK;
     }
     if (p->search_stats) return TAFL_OK;
@@ -850,6 +882,49 @@ int tafl_pool_gather_stats(tafl_pool* p, const uint32_t* slot, uint32_t count, f
                        p->first_live(), (unsigned long long)p->book.live, p->mem.C, dv, ds);
     HIPCHK(hipGetLastError());
     if (!ptrs_are_device) { COPY_OUT(value, dv, count, s); COPY_OUT(surprise, ds, count, s); HIPCHK(hipStreamSynchronize(s)); }
+    return TAFL_OK;
+}
+
+int tafl_pool_set_value_targets(tafl_pool* p, int on) {
+    POOLCHK(p, "tafl_pool_set_value_targets");
+    if (p->book.live != 0) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_set_value_targets: the pool holds live rows (the setting changes only while live == 0)");
+    hipStream_t s = p->ctx->stream;
+    if (!on) {
+        HIPCHK(hipStreamSynchronize(s));
+        for (DevBuf* d : {&p->t_vt, &p->t_kind, &p->g_k}) { p->device_bytes -= d->cap; d->release(); }
+        p->value_targets = false;
+        return TAFL_OK;
+    }
+    if (!p->search_stats) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_set_value_targets: search statistics are off (tafl_pool_set_search_stats)");
+    if (p->value_targets) return TAFL_OK;
+    if (p->need(p->t_vt, 4 * (size_t)p->mem.C) || p->need(p->t_kind, (size_t)p->mem.C)) {
+        for (DevBuf* d : {&p->t_vt, &p->t_kind}) { p->device_bytes -= d->cap; d->release(); }
+        return fail(TAFL_ERR_OOM, "hipMalloc failed (tafl_pool_set_value_targets)");
+    }
+    HIPCHK(hipMemsetAsync(p->t_vt.p, 0, 4 * (size_t)p->mem.C, s));
+    HIPCHK(hipMemsetAsync(p->t_kind.p, 0, (size_t)p->mem.C, s));
+    p->value_targets = true;
+    return sync_ok(p->ctx);
+}
+
+int tafl_pool_gather_targets(tafl_pool* p, const uint32_t* slot, uint32_t count, float* target, uint8_t* kind, int ptrs_are_device) {
+    POOLCHK(p, "tafl_pool_gather_targets");
+    if (!p->value_targets) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_targets: value targets are off (tafl_pool_set_value_targets)");
+    if (!slot && count) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_targets: null slot");
+    if (count == 0) return TAFL_OK;
+    hipStream_t s = p->ctx->stream;
+    float* dt = target; uint8_t* dk = kind;
+    if (!ptrs_are_device) {
+        for (uint32_t i = 0; i < count; ++i)
+            if (!pool_slot_live(slot[i], p->book.written, p->book.live, p->mem.C)) return fail(TAFL_ERR_INVALID_ARG, "tafl_pool_gather_targets: slot " + std::to_string(slot[i]) + " (row " + std::to_string(i) + ") is not live");
+        POOLNEED(p->g_slot, 4 * (size_t)count); POOLNEED(p->g_z, 4 * (size_t)count); POOLNEED(p->g_k, count);
+        HIPCHK(hipMemcpyAsync(p->g_slot.p, slot, 4 * (size_t)count, hipMemcpyHostToDevice, s));
+        slot = p->g_slot.as<const uint32_t>(); dt = target ? p->g_z.as<float>() : nullptr; dk = kind ? p->g_k.as<uint8_t>() : nullptr;
+    }
+    hipLaunchKernelGGL(k_pool_gather_targets, dim3(poolw_grid(count)), dim3(256), 0, s, p->t_vt.as<const float>(), p->t_kind.as<const uint8_t>(), p->mem.counters, slot, count,
+                       p->first_live(), (unsigned long long)p->book.live, p->mem.C, dt, dk);
+    HIPCHK(hipGetLastError());
+    if (!ptrs_are_device) { COPY_OUT(target, dt, count, s); COPY_OUT(kind, dk, count, s); HIPCHK(hipStreamSynchronize(s)); }
     return TAFL_OK;
 }
 

@@ -73,19 +73,23 @@ class BatchedGameLogic:
             b.reset_fen(fen, self.rules.starting_side if side_to_play is None else side_to_play)
         return b
 
-    def new_examples(self, n_games: int, max_moves: int, max_children: int, search_stats: bool = False) -> "Examples":
+    def new_examples(self, n_games: int, max_moves: int, max_children: int, search_stats: bool = False, value_targets: bool = False) -> "Examples":
         """A device-resident buffer of training examples for batches of `n_games` games: room for `max_moves` examples per game with up
         to `max_children` policy entries each (max_children >= n_sims can never overflow).  Filled by GameBatch.selfplay_record.
         search_stats: guided self-play runs also keep Qsa and the prior of every stored child (Examples.read_stats, .gather_stats);
-        rollout-mode recording refuses such an object."""
-        return Examples(self, n_games, max_moves, max_children, search_stats)
+        rollout-mode recording refuses such an object.
+        value_targets (needs search_stats): episode boundaries are kept too, and Examples.value_targets computes a TD(lambda) value
+        target per example."""
+        return Examples(self, n_games, max_moves, max_children, search_stats, value_targets)
 
-    def new_pool(self, capacity: int, max_children: int, search_stats: bool = False) -> "Pool":
+    def new_pool(self, capacity: int, max_children: int, search_stats: bool = False, value_targets: bool = False) -> "Pool":
         """A training pool on the device: a ring of `capacity` finished examples with up to `max_children` policy entries each, filled by
         Pool.ingest from Examples objects and sampled by Pool.sample (tafl_pool_*).  search_stats: Pool.set_search_stats(True)."""
         p = Pool(self, capacity, max_children)
         if search_stats:
             p.set_search_stats(True)
+        if value_targets:
+            p.set_value_targets(True)
         return p
 
     def state_from_fen(self, fen: str, side_to_play: int | None = None) -> TaflState:
@@ -609,12 +613,13 @@ class Examples:
     """Training examples (board, side to move, sparse search policy, play, result z) in HBM (tafl_examples).  Example j of game g has the
     index j * n_games + g.  The object outlives runs and batches: an episode may be recorded in several runs, a trainer may keep several."""
 
-    def __init__(self, logic: BatchedGameLogic, n_games: int, max_moves: int, max_children: int, search_stats: bool = False):
+    def __init__(self, logic: BatchedGameLogic, n_games: int, max_moves: int, max_children: int, search_stats: bool = False, value_targets: bool = False):
         self.logic = logic
         self.n_games, self.max_moves, self.max_children = n_games, max_moves, max_children
-        self.search_stats = bool(search_stats)
+        self.search_stats, self.has_value_targets = bool(search_stats), bool(value_targets)
         self._h = C.c_void_p()
-        check(lib().tafl_examples_create_ex(logic._h, n_games, max_moves, max_children, abi.EXAMPLES_SEARCH_STATS if search_stats else 0, C.byref(self._h)))
+        flags = (abi.EXAMPLES_SEARCH_STATS if search_stats else 0) | (abi.EXAMPLES_VALUE_TARGETS if value_targets else 0)
+        check(lib().tafl_examples_create_ex(logic._h, n_games, max_moves, max_children, flags, C.byref(self._h)))
         logic._batches.add(self)          # closed with the context, like its batches
 
     def close(self):
@@ -695,6 +700,40 @@ class Examples:
         value, surprise = np.zeros(k, np.float32), np.zeros(k, np.float32)
         check(lib().tafl_examples_gather_stats(self._h, idx.ctypes.data_as(vp), k, value.ctypes.data_as(vp), surprise.ctypes.data_as(vp), 0))
         return value, surprise
+
+    def value_targets(self, lam: float, settle_unfinished: bool = False) -> abi.TaflValueTargetsResult:
+        """A TD(lambda) value target per example from the search values of the positions that follow it in its episode, ending in the
+        result of a finished game or, for a cut or open episode, in its last search value (tafl_examples_value_targets; needs
+        value_targets).  settle_unfinished: the rows of unfinished episodes also get that last value as z and final = 2, so that
+        Pool.ingest takes them.  Returns episodes_closed, episodes_unfinished, rows_with_target, rows_settled.  The result stands
+        until clear(), finalize() or the next run that records into the object."""
+        cfg, out = abi.TaflValueTargetsCfg(lam=lam, flags=abi.VT_SETTLE_UNFINISHED if settle_unfinished else 0), abi.TaflValueTargetsResult()
+        check(lib().tafl_examples_value_targets(self._h, C.byref(cfg), C.byref(out)))
+        return out
+
+    def gather_targets(self, index, device: bool = False):
+        """(target float32 [k], kind uint8 [k], ep_end uint8 [k]) of the examples `index`: the value target, 0 / 1 / 2 for no target /
+        from a closed episode / from an unfinished one, and 1 for the last example of an episode (tafl_examples_gather_targets).
+        device as in gather()."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            idx = index.contiguous()
+            if idx.dtype != torch.int32 or not idx.is_cuda or idx.device.index != self.logic.device:
+                raise ValueError("gather_targets(device=True): index must be an int32 tensor on the context's device")
+            k = int(idx.numel())
+            target = torch.empty((k,), dtype=torch.float32, device=idx.device)
+            kind, ep_end = torch.empty((k,), dtype=torch.uint8, device=idx.device), torch.empty((k,), dtype=torch.uint8, device=idx.device)
+            torch.cuda.current_stream(idx.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_examples_gather_targets(self._h, vp(idx.data_ptr()), k, vp(target.data_ptr()), vp(kind.data_ptr()), vp(ep_end.data_ptr()), 1))
+            self.logic.sync()
+            return target, kind, ep_end
+        import numpy as np
+        idx = np.ascontiguousarray(index, dtype=np.uint32)
+        k = int(idx.size)
+        target, kind, ep_end = np.zeros(k, np.float32), np.zeros(k, np.uint8), np.zeros(k, np.uint8)
+        check(lib().tafl_examples_gather_targets(self._h, idx.ctypes.data_as(vp), k, target.ctypes.data_as(vp), kind.ctypes.data_as(vp), ep_end.ctypes.data_as(vp), 0))
+        return target, kind, ep_end
 
     def gather(self, index, sym=None, device: bool = False):
         """Minibatch rows (boards uint8 [k, n, n], sides uint8 [k], pi float32 [k, action_size], z float32 [k], final uint8 [k]) of the
@@ -950,6 +989,31 @@ class Pool:
         value, surprise = np.zeros(k, np.float32), np.zeros(k, np.float32)
         check(lib().tafl_pool_gather_stats(self._h, sl.ctypes.data_as(vp), k, value.ctypes.data_as(vp), surprise.ctypes.data_as(vp), 0))
         return value, surprise
+
+    # ---- value targets per row (tafl_pool_set_value_targets / _gather_targets) ----
+    def set_value_targets(self, on: bool = True):
+        """The pool carries the value target and its kind of every row it ingests (only from Examples created with value_targets whose
+        value_targets() result stands).  Needs search statistics on; allowed while the pool holds no live row; clear() keeps the setting."""
+        check(lib().tafl_pool_set_value_targets(self._h, int(bool(on))))
+
+    def gather_targets(self, slots, device: bool = False):
+        """(target float32 [k], kind uint8 [k]) of the rows in `slots`, with the rules of gather_stats for slots that are not live."""
+        vp = C.c_void_p
+        if device:
+            import torch
+            sl = self._device_u32(slots, "gather_targets(device=True): slots")
+            k = int(sl.numel())
+            target, kind = torch.empty((k,), dtype=torch.float32, device=sl.device), torch.empty((k,), dtype=torch.uint8, device=sl.device)
+            torch.cuda.current_stream(sl.device).synchronize()          # the library writes on its own stream
+            check(lib().tafl_pool_gather_targets(self._h, vp(sl.data_ptr()), k, vp(target.data_ptr()), vp(kind.data_ptr()), 1))
+            self.logic.sync()
+            return target, kind
+        import numpy as np
+        sl = np.ascontiguousarray(slots, dtype=np.uint32)
+        k = int(sl.size)
+        target, kind = np.zeros(k, np.float32), np.zeros(k, np.uint8)
+        check(lib().tafl_pool_gather_targets(self._h, sl.ctypes.data_as(vp), k, target.ctypes.data_as(vp), kind.ctypes.data_as(vp), 0))
+        return target, kind
 
     def weights_from_surprise(self, base: int, per_nat: float, generation: int = 0):
         """Every live row of ingest `generation` (0: every live row) gets the weight min(2^32 - 1, base + floor(surprise * per_nat)): an

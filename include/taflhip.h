@@ -479,8 +479,44 @@ int tafl_mcts_policy_device_ex(tafl_batch* b, double temp, uint64_t tie_seed, ui
  * tafl_examples_gather_stats: value[i], surprise[i] of example index[i], one kernel, one lane per row (either output may be NULL).  Host
  *   and device pointers as in tafl_examples_gather: a bad index fails the call with host pointers; with device pointers it writes zeros
  *   and is counted in tafl_examples_stats.bad_index.  An object without the flag: TAFL_ERR_INVALID_ARG.
- *   The training pool carries the two scalars and turns surprise into weights: tafl_pool_set_search_stats below. */
+ *   The training pool carries the two scalars and turns surprise into weights: tafl_pool_set_search_stats below.
+ *
+ * Value targets from search values (TD(lambda) per episode; the text of this block is normative).
+ * TAFL_EXAMPLES_VALUE_TARGETS (with TAFL_EXAMPLES_SEARCH_STATS; alone: TAFL_ERR_UNSUPPORTED) adds per example one byte ep_end, one float32
+ *   vt and one byte kind (6 bytes per example), and 32 bytes of result counters, all counted in device_bytes.  Without the flag nothing of
+ *   this block is allocated, launched or read.
+ * Episode boundaries: ep_end[j * G + g] = 1 iff j + 1 is a value the lane's open_from (the first example of its open episode: an episodes
+ *   run sets it to the lane's example count whenever it closes or cuts an episode) has held since the last tafl_examples_clear while it was
+ *   at or below the lane's example count.  One more kernel, one lane per game, marks it at the begin of a run and after every round and
+ *   its reopen; the self-play rounds are what they were.  An episode without a recorded example leaves no mark; a lane of a run without
+ *   episodes is one episode.
+ * tafl_examples_value_targets(ex, cfg, out): per lane g the examples 0 .. min(len, max_moves) - 1 are split into episodes after every ep_end.
+ *   An example takes part iff the N of its value (above) is > 0; the others get vt = 0, kind = 0 and are skipped.  For the participants
+ *   i = 0 .. n-1 of one episode, ascending:  s_i = +1.0 if the side to move is TAFL_ATTACKER, else -1.0;  v_i = (double)value_i;
+ *   u_i = s_i * v_i;  d_i = move_no_{i+1} - move_no_i clamped to 1 .. 65535.  The episode is closed iff final of its last participant is 1,
+ *   otherwise unfinished (cut, or still open).
+ *     lam_pow(d):  r = 1.0; b = lambda; for bit 0 .. 15: { if (d >> bit & 1) r = r * b;  b = b * b; }   (sixteen steps; lam_pow(1) == lambda)
+ *     at i = n-1: A = 0.0, L = 1.0;  for i = n-2 down to 0:  p = lam_pow(d_i);  A = (1.0 - p) * u_{i+1} + p * A;  L = p * L
+ *     T_i = closed ? (double)z_i : s_i * u_{n-1};   vt_i = (float)(s_i * A + L * T_i);   kind_i = closed ? 1 : 2
+ *   All in float64 without fused multiply-add: vt is defined bit for bit.  lambda = 1 gives z on closed episodes and the last search
+ *   value seen from the row's side on unfinished ones; lambda = 0 gives the next participant's value seen from the row's side.
+ *   lambda outside [0, 1] (NaN included): TAFL_ERR_INVALID_ARG; unknown flag bits or non-zero reserved words: TAFL_ERR_UNSUPPORTED; an
+ *   object without the flag: TAFL_ERR_INVALID_ARG.  out (may be NULL): episodes that hold a participant, closed and unfinished; the
+ *   participants; the rows settled.
+ *   TAFL_VT_SETTLE_UNFINISHED: the participants of unfinished episodes also get z_i = (float)(s_i * u_{n-1}) and final_i = 2, so that a
+ *   following tafl_pool_ingest takes them (it takes final != 0) and tafl_examples_gather shows final = 2 for them.  A later
+ *   tafl_examples_finalize rewrites the open tail from open_from on and undoes the settlement there.
+ *   The result stands until tafl_examples_clear, tafl_examples_finalize or the begin - and every later round - of a run that records
+ *   into the object, so the call belongs after the run (and, as for every recording run, the object must outlive the run: destroy it
+ *   after tafl_gselfplay_end); then it is stale, and its readers (target and kind of tafl_examples_gather_targets, tafl_pool_ingest of a pool that carries targets) refuse it
+ *   with TAFL_ERR_INVALID_ARG.
+ * tafl_examples_gather_targets: target[i] = vt, kind[i], ep_end[i] of example index[i], one lane per row, any output may be NULL; host and
+ *   device pointers and bad indices as in tafl_examples_gather_stats.  ep_end alone can be read while the result is stale. */
 #define TAFL_EXAMPLES_SEARCH_STATS 0x1u          /* tafl_examples_create_ex: keep Qsa and Ps of every stored child */
+#define TAFL_EXAMPLES_VALUE_TARGETS 0x2u         /* tafl_examples_create_ex: episode boundaries and a value target per example */
+#define TAFL_VT_SETTLE_UNFINISHED 0x1u           /* tafl_value_targets_cfg.flags */
+typedef struct tafl_value_targets_cfg { double lambda; uint32_t flags; uint32_t _reserved[5]; } tafl_value_targets_cfg;      /* 32 bytes */
+typedef struct tafl_value_targets_result { uint64_t episodes_closed, episodes_unfinished, rows_with_target, rows_settled; } tafl_value_targets_result;   /* 32 bytes */
 typedef struct tafl_examples tafl_examples;      /* opaque, owned by the ctx's device */
 typedef struct tafl_selfplay_opts {
     uint64_t sample_seed;
@@ -513,6 +549,8 @@ int tafl_examples_gather(tafl_examples* ex, const uint32_t* index, const uint8_t
 int tafl_examples_create_ex(tafl_ctx* ctx, uint32_t n_games, uint32_t max_moves, uint32_t max_children, uint32_t flags, tafl_examples** out);
 int tafl_examples_read_stats(tafl_examples* ex, const uint32_t* index, uint32_t count, float* q, float* prior);
 int tafl_examples_gather_stats(tafl_examples* ex, const uint32_t* index, uint32_t count, float* value, float* surprise, int ptrs_are_device);
+int tafl_examples_value_targets(tafl_examples* ex, const tafl_value_targets_cfg* cfg, tafl_value_targets_result* out);
+int tafl_examples_gather_targets(tafl_examples* ex, const uint32_t* index, uint32_t count, float* target, uint8_t* kind, uint8_t* ep_end, int ptrs_are_device);
 
 /* ---- guided MCTS: src/mcts.py:55-136 with the CALLER's network as nnet.predict (mcts.py:85), SURVEY.md section 8f rank 3 ---
  * Lock-step over the batch: each tafl_gmcts_step (i) expands every waiting leaf with the priors / value the caller computed
@@ -1047,6 +1085,14 @@ int tafl_gmcts_leaf_symmetry(tafl_batch* b, uint8_t* out_sym, int out_is_device)
  *   which is an ASSIGNMENT, not the maximum rule of tafl_pool_set_weights; the other slots are unchanged.  One kernel over the slots on
  *   the context's stream, nothing is read back; the sums behind the weighted search are rebuilt by the next weighted sample, as after
  *   tafl_pool_set_weights.
+ * Value targets (off by default).  tafl_pool_set_value_targets(pool, on): allowed only while live == 0 and only with search statistics on
+ *   (otherwise TAFL_ERR_INVALID_ARG).  On allocates float32 vt[capacity] and uint8 kind[capacity] beside the rows; device_bytes counts the
+ *   5 * capacity bytes, the row layout does not change, tafl_pool_clear keeps the setting, switching search statistics off switches it
+ *   off too.  While it is on, tafl_pool_ingest refuses (TAFL_ERR_INVALID_ARG, nothing is taken) an examples object without
+ *   TAFL_EXAMPLES_VALUE_TARGETS or whose targets are stale, and one more pass of its own (the rank and the placement of the pass that
+ *   writes value and surprise) copies vt and kind of every row the ingest stores.  A trim and a wrap treat the two arrays as they treat value and surprise.
+ * tafl_pool_gather_targets: target[i], kind[i] of the row in slot[i] (either may be NULL), with the rules of tafl_pool_gather_stats for
+ *   slots that are not live.  The setting off: TAFL_ERR_INVALID_ARG.
  * De-duplication of positions (nothing of it exists until the first tafl_pool_dedup; the rows of the ring are never moved or merged).
  * tafl_pool_dedup(pool, cfg, out) groups the live rows [written - live, written) as they are at the call.  For a row with board bytes
  *   b[t], t < n^2 (n = side_len) and side to move `side` (TAFL_ATTACKER / TAFL_DEFENDER as tafl_pool_gather writes it):
@@ -1146,6 +1192,8 @@ typedef struct tafl_pool_surprise_weights {
 int tafl_pool_set_search_stats(tafl_pool* pool, int on);                              /* 0: off (the default) */
 int tafl_pool_gather_stats(tafl_pool* pool, const uint32_t* slot, uint32_t count, float* value, float* surprise, int ptrs_are_device);
 int tafl_pool_weights_from_surprise(tafl_pool* pool, const tafl_pool_surprise_weights* cfg);
+int tafl_pool_set_value_targets(tafl_pool* pool, int on);                             /* 0: off (the default) */
+int tafl_pool_gather_targets(tafl_pool* pool, const uint32_t* slot, uint32_t count, float* target, uint8_t* kind, int ptrs_are_device);
 #define TAFL_POOL_DEDUP_SYMMETRIES 0x1u        /* tafl_pool_dedup: positions that are images of each other under a board symmetry are one group */
 typedef struct tafl_pool_dedup_cfg {
     uint32_t flags;            /* 0 or TAFL_POOL_DEDUP_SYMMETRIES */
